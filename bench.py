@@ -9,6 +9,12 @@ Workload (N=1 default): BASELINE.json configs[1], Pong NIPS ec=32 ew=8 t_max=5, 
 
   python bench.py [--gpus N --steps K --warmup W --config pong-nips --sampling device]
   N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, settles, warms up, times the K steps and prints the result line (the headline
+figure + what the timed loop itself recorded). --full adds every other measurement and check, each
+a run of its own after the timed region: the roofline / per-kernel / train-pass timings, the trunk
+batch sweep, the data-parallel replica check and all-reduce timing, and the CPU baselines.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -376,11 +382,131 @@ def time_allreduce(learner, world, dist):
         return {'error': repr(e)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+# --dump-outputs: the settle phase is this many updates instead of --settle_s seconds of them (a
+# count read off a clock differs from run to run, and with it every array of the last step)
+DUMP_SETTLE_UPDATES = 2000
+
+
+def dump_outputs(learner, out_dir):
+    """What the last timed step (rollout + update) left its caller, as <out_dir>/<name>.npy in
+    float32: the rollout's values, policy outputs, sampled action / repetition indices, clipped
+    rewards and masks; the update's n-step returns, advantages and per-row loss terms, its gradient,
+    and the parameters and RMSProp accumulator after it. At most DUMP_LIMIT_BYTES in all: beyond that
+    every array larger than its equal share is cut to a seeded sample of its elements (sorted flat
+    indices, the same from run to run)."""
+    import torch
+    torch.cuda.synchronize()
+    T = learner.max_local_steps
+    net = learner.network
+    arrays = {
+        'values': learner.values, 'pi': learner.pi_all[:T], 'rep': learner.rep_all[:T],
+        'actions': learner.idx[0], 'repetitions': learner.idx[1],
+        'rewards': learner.rm_h[0], 'masks': learner.rm_h[1],
+        'returns': learner.y, 'advantages': learner.adv, 'loss_terms': learner.loss_terms,
+        'grad': net.grad, 'params': net.params, 'rmsprop_ms': net.ms,
+    }
+    return write_outputs({k: t.detach().cpu().numpy() for k, t in arrays.items()}, out_dir)
+
+
+def write_outputs(arrays, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """The arrays as <out_dir>/<name>.npy in float32, within limit_bytes in all (dump_outputs);
+    returns name -> written shape."""
+    arrays = {k: np.ascontiguousarray(np.asarray(x).astype(np.float32)) for k, x in arrays.items()}
+    if sum(x.nbytes for x in arrays.values()) > limit_bytes:
+        share = limit_bytes // (4 * len(arrays))  # elements
+        rs = np.random.RandomState(0)
+        for k in sorted(arrays):
+            if arrays[k].size > share:
+                arrays[k] = arrays[k].reshape(-1)[np.sort(rs.choice(arrays[k].size, share, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), x)
+    return {k: list(x.shape) for k, x in arrays.items()}
+
+
+def headline(a, cfg, world, value, elapsed, learner_dp, settle):
+    """The result line's headline fields (every run prints them; --full adds to them)."""
+    ec, T = cfg['ec'], a.t_max
+    return {
+        'metric': 'env-steps/sec (ec x t_max frames per update)',
+        'value': round(value, 1),
+        'unit': 'env-steps/s',
+        'n_gpus': world,
+        'steps': a.steps,
+        'warmup': a.warmup,
+        'ms_per_step': round(elapsed / a.steps * 1e3, 4),
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': 'fp32',
+        'data': 'synthetic emulators (seeded 210x160 screen rings, manette_amd/synthetic.py; no ALE): host '
+                'emulator threads pool + resize each push to 84x84, the GPU stacks the 4-frame states and runs '
+                'forward, sampling, returns, backward and RMSProp; random-init weights. The emulators are '
+                'near-free, so this is an upper bound for real ALE games (learner_only, with --full, isolates '
+                'the GPU side)',
+        'config': {'workload': '%s ec=%d ew=%d t_max=%d per GPU, %s sampling, %s step, %s staging%s%s' % (
+            a.config, ec, cfg['ew'], T, a.sampling, a.step_impl, a.staging, ', pipelined' if a.pipeline else '',
+            ', data-parallel update forced at world 1 (RCCL)' if a.dp_force and world == 1 else ''),
+            'arch': cfg['arch'], 'emulators_per_gpu': ec,
+            'global_emulators': ec * world, 'parallelism': 'dp%d' % world,
+            'dp_update': bool(learner_dp), 'settle_updates': settle},
+    }
+
+
+def timed_loop_fields(a, cfg, world, t0, marks, w, window_phases, every_threads, step_phases, emu_split, workers):
+    """What the timed loop recorded about itself (no run of their own): the value of its
+    sub-windows, the host threads' placement and the per-macro-step host phases."""
+    ec, T = cfg['ec'], a.t_max
+    edges = [t0] + marks
+    wins = [world * ec * T * w / (edges[i + w] - edges[i]) for i in range(0, a.steps - w + 1, w)]
+    out = {
+        'value_windows': {'updates_per_window': w, 'values': [round(v, 1) for v in wins],
+                          'spread': round((max(wins) - min(wins)) / float(np.median(wins)), 4),
+                          'host_phases_us': window_phases,
+                          'note': 'env-steps/s of consecutive sub-windows of the timed region (host clock after '
+                                  'each update; the rollout waits on the device every macro-step), with each '
+                                  'window\'s per-macro-step host phases (launch_and_wait = the GPU chain as the '
+                                  'host sees it, emulators = the emulator threads)'},
+        'host_threads': {'per_rank': every_threads,
+                         'note': 'emulator worker threads + the host thread of each rank: its cpu slice '
+                                 '(the allowed cpus on its GPU\'s NUMA node, split between the local ranks '
+                                 'sharing it), the cores it may use (slice, container quota / local ranks), '
+                                 'ew after the oversubscription cap, and whether they were pinned '
+                                 '(--pin_threads auto: only with several ranks per node)'},
+    }
+    if step_phases:
+        if emu_split:  # what the emulator threads spend per step (averaged over workers)
+            step_phases['emulator_threads'] = {
+                'staging_us_per_worker': round(emu_split['stage_us'], 2),
+                'busy_us_per_worker': round(emu_split['busy_us'], 2),
+                'workers': workers,
+                'note': 'per worker per macro-step: staging = %s; busy = the whole step phase (staging + '
+                        'the synthetic emulation, FiGAR repeats and per-env publication); emulators_us = the '
+                        'step\'s wall time to its last worker' % (
+                            'frame pool + nearest resize + streaming copy of each push\'s 84x84 frame'
+                            if a.staging == 'resized' else 'the copy of the staged screen rows')}
+        out['macro_step_host_us'] = step_phases
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=60)
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run every other measurement and check: roofline, '
+                         'per-kernel and train-pass timings, trunk batch sweep, replica check and all-reduce '
+                         'timing (N > 1), CPU baselines (--cpu_seconds, --no_cpu_baseline, --measure_updates '
+                         'and --trunk_sweep shape them)')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32; '
+                         'dump_outputs); the settle phase is then a fixed number of updates, so the same '
+                         'arguments give the same inputs from run to run')
+    ap.add_argument('--settle_updates', type=int, default=None,
+                    help='settle for this many updates instead of --settle_s seconds (default with '
+                         '--dump-outputs: %d)' % DUMP_SETTLE_UPDATES)
     ap.add_argument('--config', default='pong-nips', choices=sorted(CONFIGS))
     ap.add_argument('--t_max', type=int, default=5)
     ap.add_argument('--sampling', default='device', choices=['device', 'host'])
@@ -412,6 +538,8 @@ def main():
     ap.add_argument('--trunk_sweep', default='256,1024,4096',
                     help='extra batch sizes the trunk kernel is timed at after the run ("" = none)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     import torch
     import torch.distributed as dist
@@ -446,7 +574,12 @@ def main():
         with comm_.Deadline('the first data-parallel update (all-reduce of the gradient)', rank, world):
             one_update()
             torch.cuda.synchronize()
-    settle = settle_updates(one_update, a.settle_s, world, dist)
+    settle = a.settle_updates if a.settle_updates is not None else DUMP_SETTLE_UPDATES if a.dump_outputs else None
+    if settle is None:
+        settle = settle_updates(one_update, a.settle_s, world, dist)
+    else:  # a fixed count: every run (and every rank) sees the same updates
+        for _ in range(settle):
+            one_update()
     for _ in range(a.warmup):
         one_update()
     if world > 1:
@@ -503,7 +636,27 @@ def main():
         dist.all_gather_object(every_threads, threads)
     else:
         every_threads = [threads]
-    # ---- measurements after the timed region (none of them is part of `value`) ----------------
+    ec = cfg['ec']
+    value = world * ec * T * a.steps / elapsed
+    dumped = None
+    if a.dump_outputs and rank == 0:  # before anything below runs another update
+        dumped = dump_outputs(learner, a.dump_outputs)
+    line = None
+    if rank == 0:
+        line = headline(a, cfg, world, value, elapsed, learner_dp, settle)
+        line.update(timed_loop_fields(a, cfg, world, t0, marks, w, window_phases, every_threads, step_phases,
+                                      emu_split, learner.workers))
+        if dumped is not None:
+            line['dumped_outputs'] = {'dir': a.dump_outputs, 'shapes': dumped}
+    if not a.full:  # a plain run ends here
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        learner.cleanup()
+        shutil.rmtree(args.debugging_folder, ignore_errors=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # ---- --full: measurements after the timed region (none of them is part of `value`) --------
     prof = {}
     # (1) roofline kernels where the timed loop runs them: the native rollout records an event
     #     pair around every step forward's trunk launches (NIPS: the stacking conv kernel + the
@@ -629,8 +782,6 @@ def main():
                                                          3))) * 1e-3))
             del obs_b
             net._ws.pop(('sweep', Eb), None)
-    ec = cfg['ec']
-    value = world * ec * T * a.steps / elapsed
 
     if rank == 0:
         depth = 3 if cfg['rgb'] else 1
@@ -777,31 +928,7 @@ def main():
         kernels.append(row('A11', 'actor_learner.py:55-74', 'clip_rmsprop_kernel', med(prof['clip_rmsprop']),
                            28 * P_ + 4 * 512 + 4, note='%d params: w, ms, mom, g read (16 B) and w, ms, mom written '
                            '(12 B) per parameter; ' % P_ + graph_note))
-        # the timed region in sub-windows (host clock after each update)
-        edges = [t0] + marks
-        wins = [world * ec * T * w / (edges[i + w] - edges[i]) for i in range(0, a.steps - w + 1, w)]
-        line = {
-            'metric': 'env-steps/sec (ec x t_max frames per update)',
-            'value': round(value, 1),
-            'unit': 'env-steps/s',
-            'n_gpus': world,
-            'steps': a.steps,
-            'warmup': a.warmup,
-            'ms_per_step': round(elapsed / a.steps * 1e3, 4),
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'fp32',
-            'data': 'synthetic emulators (seeded 210x160 screen rings, manette_amd/synthetic.py; no ALE): host '
-                    'emulator threads pool + resize each push to 84x84, the GPU stacks the 4-frame states and runs '
-                    'forward, sampling, returns, backward and RMSProp; random-init weights. The emulators are '
-                    'near-free, so this is an upper bound for real ALE games (learner_only isolates the GPU side)',
-            'config': {'workload': '%s ec=%d ew=%d t_max=%d per GPU, %s sampling, %s step, %s staging%s%s' % (
-                a.config, ec, cfg['ew'], T, a.sampling, a.step_impl, a.staging, ', pipelined' if a.pipeline else '',
-                ', data-parallel update forced at world 1 (RCCL)' if a.dp_force and world == 1 else ''),
-                'arch': cfg['arch'], 'emulators_per_gpu': ec,
-                'global_emulators': ec * world, 'parallelism': 'dp%d' % world,
-                'dp_update': bool(learner_dp), 'settle_updates': settle},
+        line.update({
             # bound = the resource the trunk's arithmetic intensity binds on the roofline (fp32 ridge
             # 157.3 TFLOP/s / 8 TB/s = 19.7 FLOP/B; NIPS E=32: 52 FLOP/B -> mfma); both fractions kept
             'roofline': dict(
@@ -841,20 +968,7 @@ def main():
             'rollout_forward': {'ms': round(rf_ms, 4), 'tflops': round(fwd_flops / (rf_ms * 1e-3) / 1e12, 3),
                                 'hbm_gbs': round(fwd_bytes / (rf_ms * 1e-3) / 1e9, 1),
                                 'hbm_frac': round(fwd_bytes / (rf_ms * 1e-3) / 1e9 / MI355X_HBM_GBS, 4)},
-            'value_windows': {'updates_per_window': w, 'values': [round(v, 1) for v in wins],
-                              'spread': round((max(wins) - min(wins)) / float(np.median(wins)), 4),
-                              'host_phases_us': window_phases,
-                              'note': 'env-steps/s of consecutive sub-windows of the timed region (host clock after '
-                                      'each update; the rollout waits on the device every macro-step), with each '
-                                      'window\'s per-macro-step host phases (launch_and_wait = the GPU chain as the '
-                                      'host sees it, emulators = the emulator threads)'},
-        }
-        line['host_threads'] = {'per_rank': every_threads,
-                                'note': 'emulator worker threads + the host thread of each rank: its cpu slice '
-                                        '(the allowed cpus on its GPU\'s NUMA node, split between the local ranks '
-                                        'sharing it), the cores it may use (slice, container quota / local ranks), '
-                                        'ew after the oversubscription cap, and whether they were pinned '
-                                        '(--pin_threads auto: only with several ranks per node)'}
+        })
         if replicas is not None:
             line['replicas_identical'] = replicas
         if allreduce is not None:
@@ -870,18 +984,6 @@ def main():
                  'tflops': round(Eb * per_env_flops / (ms * 1e-3) / 1e12, 2),
                  'flop_frac': round(Eb * per_env_flops / (ms * 1e-3) / 1e12 / MI355X_FP32_TFLOPS, 4)}
                 for Eb, ms in sweep]
-        if step_phases:
-            if emu_split:  # what the emulator threads spend per step (averaged over workers)
-                step_phases['emulator_threads'] = {
-                    'staging_us_per_worker': round(emu_split['stage_us'], 2),
-                    'busy_us_per_worker': round(emu_split['busy_us'], 2),
-                    'workers': learner.workers,
-                    'note': 'per worker per macro-step: staging = %s; busy = the whole step phase (staging + '
-                            'the synthetic emulation, FiGAR repeats and per-env publication); emulators_us = the '
-                            'step\'s wall time to its last worker' % (
-                                'frame pool + nearest resize + streaming copy of each push\'s 84x84 frame'
-                                if a.staging == 'resized' else 'the copy of the staged screen rows')}
-            line['macro_step_host_us'] = step_phases
         if world == 1 and not a.no_cpu_baseline:
             learner.cleanup()
             learner = None

@@ -13,7 +13,7 @@ Outputs (numpy .npz without pickles, and JSON):
   G1 host_loop_*.npz   paac.PAACLearner.train() feeds (paac.py:86-297) + episode summaries
   G2 runner.json       EmulatorRunner._run bookkeeping (emulator_runner.py:19-42)
   G3 tab_rep.json      ExplorationPolicy.get_tab_repetitions (exploration_policy.py:56-62)
-  G4 preprocess.npz    AtariEmulator frame pool / resize / stack (atari_emulator.py:79-124)
+  G4 preprocess.npz, preprocess_rgb.npz  AtariEmulator frame pool / resize / stack (atari_emulator.py:79-124)
   G5 meta_graph.json   constants + op structure decoded from pretrained/*/checkpoints/*.meta
 Usage: python tests/golden/make_golden.py [--ref /root/reference]
 """
@@ -552,7 +552,9 @@ def main():
         json.dump(run_runner(a.ref), f)
     with open(os.path.join(a.out, 'tab_rep.json'), 'w') as f:
         json.dump(run_tab_rep(), f, indent=1)
-    np.savez_compressed(os.path.join(a.out, 'preprocess.npz'), **run_preprocess())
+    pre = run_preprocess()  # two files, each under 1 MiB: the RGB stacks apart from the LUTs + gray stacks
+    np.savez_compressed(os.path.join(a.out, 'preprocess.npz'), **{k: v for k, v in pre.items() if not k.startswith('rgb_')})
+    np.savez_compressed(os.path.join(a.out, 'preprocess_rgb.npz'), **{k: v for k, v in pre.items() if k.startswith('rgb_')})
     with open(os.path.join(a.out, 'meta_graph.json'), 'w') as f:
         json.dump(run_meta(a.ref), f, indent=0, sort_keys=True)
     print('done')

@@ -115,7 +115,8 @@ def test_preprocess_lut_g4():
 
 @pytest.mark.parametrize('rgb', [False, True])
 def test_preprocess_stack_g4(rgb):
-    p = np.load(os.path.join(GOLDEN, 'preprocess.npz'))
+    # (the RGB stacks are a file of their own: one fixture file would exceed 1 MiB)
+    p = np.load(os.path.join(GOLDEN, 'preprocess_rgb.npz' if rgb else 'preprocess.npz'))
     tag = 'rgb' if rgb else 'gray'
     obs, frames, terms = p['%s_obs' % tag], p['%s_frame_after' % tag], p['%s_terms' % tag]
     depth = 3 if rgb else 1

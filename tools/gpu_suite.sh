@@ -17,7 +17,7 @@ for step in ${STEPS:-smoke tests bench}; do
   case $step in
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run tests 900 python -u -m pytest tests -x -v -m gpu --timeout 120 --timeout-method thread ;;
-    bench) run bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench) run bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     prof) run prof 600 bash tools/prof.sh ${PROF_NAME:-prof} ${PROF_ARGS:-} ;;
     pmc) run pmc 600 bash tools/pmc.sh ${PMC_NAME:-pmc} ${PMC_ARGS:-} ;;
     probe) MANETTE_HIP_LIB=$PWD/manette_amd/libmanette_hip_probe.so run probe 300 python tools/probe.py ${PROBE_ARGS:-} ;;

@@ -7,6 +7,7 @@
 set -u
 NAME=${1:-prof_driver}
 shift || true
+set -- --full "$@"  # (the labelled windows and the per-kernel figures are --full measurements)
 R=$GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 cd /tmp
