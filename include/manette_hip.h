@@ -482,7 +482,10 @@ int mt_rollout_set_update_dp(mt_rollout *ro, void *const *graph_execs, mt_comm *
                              size_t split, float *lr_host, double initial_lr, double annealing_steps);
 
 /* ---- small helpers ----------------------------------------------------------------------- */
-/* out[i] = sum_z parts[z*n + i] (deterministic order); used for split reductions. */
+/* out[i] = sum_z parts[z*n + i] (deterministic order); used for split reductions. The order, for
+ * n a multiple of 4 and 16-byte aligned parts / out: the 16 subset sums s_k = sum of the slabs
+ * z = k, k + 16, ... (in slab order) added as s_0 + s_1 + ... + s_15, which is plain slab order
+ * up to 16 slabs; otherwise (slabs off the 16-byte grid) plain slab order, one element per thread. */
 int mt_sum_slabs(const float *parts, int nslabs, size_t n, float *out, mt_stream_t stream);
 
 /* Launch window: after mt_launch_window(first, count), first >= 0, the library numbers its grouped

@@ -425,6 +425,12 @@ __device__ __forceinline__ float wave_softmax(float x, int lane, int n) {
 
 constexpr int kMaxHeads = 64;  // 1 + A + R <= 64
 constexpr int kMaxScan = 1024;  // max t_max of the fused n-step scan (mt_returns_loss_backward)
+// Dynamic LDS the heads and loss kernels may ask for: the largest head region mt_net_create accepts
+// (F = 512, A = 32, R = 31: 64 outputs x 513 rows, each (w, b) pair 64-float aligned = 131,840 bytes).
+// With loss_bwd_kernel's ~10.5 KB of static LDS (the scan buffer, the bootstrap's features) that stays
+// inside the 160 KB of a CU; a cap of 150 KB did not, and hipFuncSetAttribute refused it (invalid
+// argument), so no head region above 64 KB could run the loss kernel.
+constexpr size_t kHeadRegionMaxBytes = 132 * 1024;
 
 // draw_index (common.h) over probabilities held in lanes [0, n): same order and rounding.
 __device__ __forceinline__ int wave_draw(float p, int n, double u) {
@@ -646,7 +652,7 @@ static int launch_heads(int rows, hipStream_t s, const float *slabs, int S, int 
   }
   // dynamic LDS: the head region (<= 64 outputs x 513 rows: 132 KB at most)
   const size_t lds = (size_t)hp.nq * 16;
-  if (lds > 150 * 1024) {
+  if (lds > kHeadRegionMaxBytes) {
     set_error("heads: head region of %zu bytes exceeds the LDS", lds);
     return MT_ERR_ARG;
   }
@@ -655,7 +661,7 @@ static int launch_heads(int rows, hipStream_t s, const float *slabs, int S, int 
     static bool attr_set = false;                                                                            \
     if (!attr_set && lds > 64 * 1024) {                                                                      \
       MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&heads_fwd_kernel<FT_, SB_, NT_>),           \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));                   \
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));  \
       attr_set = true;                                                                                       \
     }                                                                                                        \
     hipLaunchKernelGGL((heads_fwd_kernel<FT_, SB_, NT_>), dim3(rows), dim3(NT_), lds, s, slabs, S, B, fc_b,    \
@@ -1419,14 +1425,14 @@ static int loss_bwd_launch(const mt_net *n, const float *P, int B, float *ws, co
   HeadParams hp = head_params(n, P);
   if (!launch_allowed()) return MT_OK;
   const size_t lds = (size_t)hp.nq * 16;  // the head region (heads kernel: same bound)
-  if (lds > 150 * 1024) {
+  if (lds > kHeadRegionMaxBytes) {
     set_error("loss: head region of %zu bytes exceeds the LDS", lds);
     return MT_ERR_ARG;
   }
   static bool attr_set = false;
   if (!attr_set && lds > 64 * 1024) {
     MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&loss_bwd_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));
     attr_set = true;
   }
   hipLaunchKernelGGL(loss_bwd_kernel, dim3(B), dim3(256), lds, s, hp, ws + L.H, pi, rep, v, a_idx, r_idx, y, adv,
@@ -2056,8 +2062,28 @@ extern "C" int mt_lstm_frames_backward(const mt_net *net, const float *params, c
   return MT_OK;
 }
 
+// mt_sum_slabs for slabs that are not rows of float4s (n not a multiple of 4, or unaligned
+// pointers): slab z starts at parts + z*n, off the 16-byte grid sum_slabs_body's vector columns
+// assume (it strides the slabs by n/4 float4s). One thread per element, slabs added in slab order.
+__global__ __launch_bounds__(256) void sum_slabs_scalar_kernel(const float *__restrict__ P, int S, size_t n,
+                                                               float *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float t = 0.f;
+  for (int z = 0; z < S; ++z) t += P[(size_t)z * n + i];
+  out[i] = t;
+}
+
 extern "C" int mt_sum_slabs(const float *parts, int nslabs, size_t n, float *out,
                             mt_stream_t stream) {
   MT_CHECK_ARG(parts && out && nslabs >= 1, "bad argument");
+  MT_CHECK_ARG(n >= 1 && n <= ((size_t)1 << 36), "n out of range");
+  if ((n & 3) != 0 || ((((uintptr_t)parts) | ((uintptr_t)out)) & 15) != 0) {
+    if (!launch_allowed()) return MT_OK;
+    hipLaunchKernelGGL(sum_slabs_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       parts, nslabs, n, out);
+    MT_LAUNCHED();
+    return MT_OK;
+  }
   return sum_slabs(parts, nslabs, n, out, (hipStream_t)stream);
 }

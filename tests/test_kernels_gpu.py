@@ -18,11 +18,11 @@ CONFIGS = [('NIPS', 1, 6, 1), ('NIPS', 3, 4, 11), ('NATURE', 1, 4, 11), ('NATURE
            ('PWYX', 1, 4, 11), ('PWYX', 3, 6, 1), ('NATURE', 1, 18, 11)]
 
 
-def _net(arch, depth, A, R, seed=0, act='relu'):
+def _net(arch, depth, A, R, seed=0, act='relu', alpha=0.1, temp=1.0, beta=0.02):
     from manette_amd.network import DeviceNetwork
-    conf = dict(arch=arch, rgb=depth == 3, num_actions=A, nb_choices=R, softmax_temp=1.0,
-                entropy_regularisation_strength=0.02, clip_norm=3.0, clip_norm_type='global',
-                activation=act, alpha_leaky_relu=0.1)
+    conf = dict(arch=arch, rgb=depth == 3, num_actions=A, nb_choices=R, softmax_temp=temp,
+                entropy_regularisation_strength=beta, clip_norm=3.0, clip_norm_type='global',
+                activation=act, alpha_leaky_relu=alpha)
     net = DeviceNetwork(conf)
     net.init_params(seed)
     return net
@@ -484,18 +484,26 @@ def test_zero_copy_reads_see_host_rewrites_across_launches():
             np.testing.assert_array_equal(got[e], preprocess.stack_update(pv[e], pushes, depth), err_msg='round %d' % it)
 
 
-@pytest.mark.parametrize('arch,E,depth', [('NIPS', 7, 1), ('NIPS', 32, 1), ('NIPS', 5, 3), ('NATURE', 7, 1),
-                                          ('NATURE', 64, 1), ('PWYX', 7, 1), ('PWYX', 5, 3), ('PWYX', 32, 3)])
-def test_stacking_trunk_in_kernel_pull(arch, E, depth):
+_STACKING = [('NIPS', 7, 1), ('NIPS', 32, 1), ('NIPS', 5, 3), ('NATURE', 7, 1), ('NATURE', 64, 1), ('PWYX', 7, 1),
+             ('PWYX', 5, 3), ('PWYX', 32, 3)]
+_STACKING_LEAKY = [('NIPS', 7, 1), ('NATURE', 7, 1), ('PWYX', 7, 1), ('PWYX', 5, 3)]  # one E per arch
+
+
+@pytest.mark.parametrize('arch,E,depth,act', [c + ('relu',) for c in _STACKING] +
+                         [c + ('leaky_relu',) for c in _STACKING_LEAKY],
+                         ids=['%s-%d-%d' % c for c in _STACKING] + ['%s-%d-%d-leaky_relu' % c for c in _STACKING_LEAKY])
+def test_stacking_trunk_in_kernel_pull(arch, E, depth, act):
     """mt_forward_trunk_stacking — the rollout chain's conv kernel (NIPS: nips_conv_kernel<STACK>;
     gray NATURE: conv1 = the direct conv with DFwdStack's patch staging; PWYX gray / RGB:
     stack_conv1_kernel's env blocks, then its conv1 tiles per env) pulling each env's frames
     from pinned host staging behind its ready word (edge cache lines read with system-scope loads):
     the stacked state == the A2 oracle (bit-exact), and the trunk outputs (conv activations + dense
-    partial slabs) == mt_forward_trunk on that state, bit for bit."""
+    partial slabs) == mt_forward_trunk on that state, bit for bit. Leaky ReLU (the chains fill their
+    activation and slope apart from the layered path): also mt_forward_infer on the stacked state
+    vs the oracle."""
     from manette_amd.network import host_device_pointer
     import ctypes as C
-    net = _net(arch, depth, 6, 11, seed=E)
+    net = _net(arch, depth, 6, 11, seed=E, act=act)
     rs = np.random.RandomState(30 + E + depth)
     counts = rs.randint(1, 5, E).astype(np.int32)
     counts[:2] = 4  # full slot groups: their last line borders the next env's first
@@ -522,6 +530,14 @@ def test_stacking_trunk_in_kernel_pull(arch, E, depth):
     net.forward_trunk(out, E, ws_key='plain')
     torch.cuda.synchronize()
     assert torch.equal(ws[:ws2.numel()], ws2)
+    if act != 'relu':
+        v, pi, rep = [t.clone() for t in net.forward(out, infer=True, ws_key='stk_infer')]
+        torch.cuda.synchronize()
+        spec = nets.arch_spec(arch, depth, 6, 11)
+        v0, pi0, rep0, _ = nets.forward(spec, net.get_variables(), got, act=act, alpha=0.1)
+        np.testing.assert_allclose(v.cpu().numpy(), v0, rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(pi.cpu().numpy(), pi0, rtol=2e-5, atol=1e-6)
+        np.testing.assert_allclose(rep.cpu().numpy(), rep0, rtol=2e-5, atol=1e-6)
 
 
 def _counter_words(net, ws, E):

@@ -22,11 +22,11 @@ from oracle import nets
 pytestmark = pytest.mark.gpu
 
 
-def _net(depth, A, R, seed, act='relu'):
+def _net(depth, A, R, seed, act='relu', alpha=0.1, temp=1.0, beta=0.02):
     from manette_amd.network import DeviceNetwork
-    conf = dict(arch='LSTM', rgb=depth == 3, num_actions=A, nb_choices=R, softmax_temp=1.0,
-                entropy_regularisation_strength=0.02, clip_norm=3.0, clip_norm_type='global',
-                activation=act, alpha_leaky_relu=0.1)
+    conf = dict(arch='LSTM', rgb=depth == 3, num_actions=A, nb_choices=R, softmax_temp=temp,
+                entropy_regularisation_strength=beta, clip_norm=3.0, clip_norm_type='global',
+                activation=act, alpha_leaky_relu=alpha)
     net = DeviceNetwork(conf)
     net.init_params(seed)
     # non-zero cell bias so every gate term is exercised (TF initialises it to zero)

@@ -8,7 +8,7 @@ import torch.nn.functional as Fn
 from oracle import nets
 
 
-def torch_loss(spec, P, obs, a_idx, r_idx, y, adv, beta, act='relu', alpha=0.1):
+def torch_loss(spec, P, obs, a_idx, r_idx, y, adv, beta, act='relu', alpha=0.1, temp=1.0):
     T = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in P.items()}
     lstm = spec.get('lstm')
     if lstm:  # [B, 5, 84, 84, C] memory windows -> 5B frames
@@ -51,10 +51,10 @@ def torch_loss(spec, P, obs, a_idx, r_idx, y, adv, beta, act='relu', alpha=0.1):
     h = torch.relu(h) if act == 'relu' else torch.maximum(h, alpha * h)
     v = (h @ T['Training/Critic/critic_output/critic_output_weights'] +
          T['Training/Critic/critic_output/critic_output_biases']).reshape(-1)
-    pi = torch.softmax(h @ T['Training/Actor/actor_output/actor_output_weights'] +
-                       T['Training/Actor/actor_output/actor_output_biases'], 1)
-    rep = torch.softmax(h @ T['Training/Repetition/repetition_output/repetition_output_weights'] +
-                        T['Training/Repetition/repetition_output/repetition_output_biases'], 1)
+    pi = torch.softmax((h @ T['Training/Actor/actor_output/actor_output_weights'] +
+                        T['Training/Actor/actor_output/actor_output_biases']) / temp, 1)  # networks.py:97
+    rep = torch.softmax((h @ T['Training/Repetition/repetition_output/repetition_output_weights'] +
+                         T['Training/Repetition/repetition_output/repetition_output_biases']) / temp, 1)
     lpi = torch.log(pi + 1e-30)
     lrep = torch.log(rep + 1e-30)
     ent = -(pi * lpi).sum(1) - (rep * lrep).sum(1)
@@ -88,6 +88,41 @@ def test_oracle_backward_vs_autograd(arch, depth, A, R, act):
     assert abs(loss - tl) < 1e-10 * max(1, abs(tl))
     for k in TG:
         np.testing.assert_allclose(G[k].reshape(TG[k].shape), TG[k], rtol=1e-8, atol=1e-12, err_msg=k)
+
+
+@pytest.mark.parametrize('temp', [0.5, 2.0])
+@pytest.mark.parametrize('arch,depth,A,R', [('NIPS', 1, 6, 3), ('PWYX', 1, 4, 11), ('LSTM', 1, 9, 11)])
+def test_oracle_temperature_and_alpha_vs_autograd(arch, depth, A, R, temp):
+    """The oracle's softmax temperature (logits / temp before both softmaxes, the 1 / temp of the
+    head gradients) and a leaky slope other than the default (alpha = 0.3: the pooled PWYX / LSTM
+    layers route max-pool gradients through it) against torch autograd in float64 — the GPU tests
+    lean on nets.loss_and_grads(temp=, alpha=) at these values. Every case has R > 1, so both
+    softmax heads carry the temperature."""
+    act, alpha = 'leaky_relu', 0.3
+    spec = nets.arch_spec(arch, depth, A, R)
+    P = {k: v.astype(np.float64) for k, v in nets.init_params(spec, 7).items()}
+    if arch == 'LSTM':
+        P['rnn/basic_lstm_cell/bias'] = np.random.RandomState(3).uniform(-0.5, 0.5, 128)
+    # the default init leaves the logits nearly flat (temp would hardly show): scale the softmax heads
+    for k in ('Training/Actor/actor_output/actor_output_weights',
+              'Training/Repetition/repetition_output/repetition_output_weights'):
+        P[k] = P[k] * 8.0
+    rs = np.random.RandomState(8)
+    B = 3
+    shape = (B, 5, 84, 84, 4 * depth) if arch == 'LSTM' else (B, 84, 84, 4 * depth)
+    obs = rs.randint(0, 256, size=shape).astype(np.uint8)
+    a_idx = rs.randint(0, A, B)
+    r_idx = rs.randint(0, R, B)
+    y = rs.randn(B)
+    adv = rs.randn(B)
+    loss, G, aux = nets.loss_and_grads(spec, P, obs, a_idx, r_idx, y, adv, 0.05, act=act, alpha=alpha, temp=temp)
+    tl, TG = torch_loss(spec, P, obs, a_idx, r_idx, y, adv, 0.05, act=act, alpha=alpha, temp=temp)
+    assert abs(loss - tl) < 1e-10 * max(1, abs(tl))
+    for k in TG:
+        np.testing.assert_allclose(G[k].reshape(TG[k].shape), TG[k], rtol=1e-8, atol=1e-12, err_msg=k)
+    # the temperature is not a no-op on this case: the same net at temp = 1 gives another policy
+    _, pi1, _, _ = nets.forward(spec, P, obs, act=act, alpha=alpha, temp=1.0)
+    assert np.abs(aux['pi'] - pi1).max() > 1e-3
 
 
 @pytest.mark.parametrize('arch,A,R', [('NIPS', 6, 1), ('NATURE', 4, 11), ('LSTM', 9, 11)])
