@@ -36,7 +36,7 @@ enum {
 };
 
 /* --arch values of train.py:100 (networks.py:178-278). */
-enum { MT_ARCH_NIPS = 0, MT_ARCH_NATURE = 1, MT_ARCH_PWYX = 2, MT_ARCH_LSTM = 3 };
+enum { MT_ARCH_NIPS = 0, MT_ARCH_NATURE = 1, MT_ARCH_PWYX = 2, MT_ARCH_LSTM = 3, MT_ARCH_BAYESIAN = 4 };
 /* --activation values of train.py:117 (networks.py:27-31). */
 enum { MT_ACT_RELU = 0, MT_ACT_LEAKY = 1 };
 /* --clip_norm_type values of train.py:96 (actor_learner.py:55-72). */
@@ -54,6 +54,7 @@ typedef struct mt_net_config {
   int32_t activation;    /* MT_ACT_* */
   float alpha_leaky;     /* --alpha_leaky_relu */
   float softmax_temp;    /* --softmax_temp (networks.py:91-98) */
+  float keep_prob;       /* --keep_percentage: BAYESIAN only, 0 < keep_prob <= 1 (the other archs ignore it) */
 } mt_net_config;
 
 typedef struct mt_net mt_net;
@@ -88,12 +89,53 @@ int mt_net_workspace_bytes(const mt_net *net, int batch, size_t *bytes);
  * maximum in (row, col) order that the backward routes the gradient to, TF MaxPoolGrad); kind 2:
  * the dense layer's output H ([rows][F] fp32); kind 3: the gradient of conv layer `layer`'s output
  * after a backward ([rows][OH][OW][COUT] fp32, full resolution); kind 4: the stacking chains' hand-off
- * counters (uint32 words, zero between launches; empty for an arch without them). Byte offset and size. layout 0 = the workspace of
+ * counters (uint32 words, zero between launches; empty for an arch without them); kinds 5-7 (BAYESIAN,
+ * layout 0): the dropout mask bytes, H3 and the dropout state, described below. Byte offset and size. layout 0 = the workspace of
  * mt_forward / mt_forward_rows on a = batch rows; layout 1 = the LSTM frame-store workspace of
  * (E = a, T = b), conv rows = fstore rows, H rows = the (T+1)E windows; layout 2 = the LSTM
  * mt_forward workspace of a windows, conv rows = window frames (window-major, 5 per window). */
 int mt_net_workspace_region(const mt_net *net, int layout, int a, int b, int kind, int layer, size_t *offset,
                             size_t *bytes);
+
+/* ---- BAYESIAN arch (networks.py:194-204, policy_v_network.py:80-81) ------------------------
+ * The NIPS trunk (conv1, conv2, fc3 2592 -> 256, activation), then
+ *   D  = tf.nn.dropout(H3, keep_prob)   binary = floor(keep_prob + U[0,1)), D = (H3 / keep_prob) * binary
+ *                                       (an fp32 division; keep_prob == 1: D = H3, no mask, no division)
+ *   H4 = act(D @ W4 + b4)               fc4 256 -> 256, variables Network_1/fc4/fc4_{weights,biases}
+ * and the three heads on H4. Dropout has no training switch in the reference: every forward draws a
+ * mask, and the train step draws a fresh one (mt_dropout_redraw). These TensorFlow facts (the dropout
+ * formula, the Network_1 scope name, the creation order conv1, conv2, fc3, fc4, critic, actor,
+ * repetition) are TF 1.x's published behaviour, not pinned by a checkpoint — as the LSTM names.
+ *
+ * Mask of one row (256 features), counter-based and salted away from mt_sample's stream; mix64 is
+ * splitmix64's finaliser (z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb;
+ * z ^= z >> 31):
+ *   base = mix64(seed ^ mix64((global_row << 40) ^ counter) ^ 0xD6E8FEB86659FD93)
+ *   for q in 0..63:  h = mix64(base + (q + 1) * 0x9e3779b97f4a7c15)
+ *     features 4q .. 4q+3 take h's four 16-bit fields, low field first: u = field * 2^-16 (exact in fp32)
+ *     keep  iff  keep_prob + u >= 1.0f    (one fp32 add: TF's floor(keep_prob + uniform))
+ *   keep_prob == 1: every feature kept.
+ * The dropout state lives in the workspace (mt_net_workspace_region kind 7, layout 0):
+ * {uint64 seed; uint64 row0; uint64 counters[rows]}. Row b's mask is keyed on (seed, row0 + b,
+ * counters[b]) and the stage increments counters[b], so each call site (workspace) has its own stream
+ * and every call draws fresh masks; the zero-filled state (seed 0) is valid. Further regions: kind 5 =
+ * the mask bytes [rows][256] uint8 (0 / 1), kind 6 = H3 [rows][256] fp32 (fc3 after bias and
+ * activation, before dropout); kind 2 stays the features the heads read (H4).
+ * mt_forward, mt_forward_infer and mt_forward_rows run the stage (mt_forward_rows: state and counters
+ * of the batch-row `ws`; H3, mask and H4 land in the train rows); mt_loss_backward runs its backward
+ * under the mask the workspace holds. mt_returns_loss_backward[_boot], mt_forward_trunk_stacking and
+ * mt_rollout_create return MT_ERR_UNSUPPORTED, as does mt_net_backward_bucket_launches. */
+
+/* out[256] = the mask of (seed, global_row, counter) at keep_prob, 0 / 1 (host restatement of the
+ * formula above; the kernels are pinned against it). */
+int mt_dropout_mask_host(uint64_t seed, uint64_t global_row, uint64_t counter, float keep_prob, uint8_t *out);
+
+/* The train step's fresh mask (the forward inside train_step, policy_v_network.py:25-74): from the
+ * H3 a forward left in rows [0, batch) of `ws`, draw new masks -> D -> fc4 -> heads into v, pi, rep,
+ * leaving the fresh mask and H4 in `ws` for the following mt_loss_backward. Neither H3 nor any conv
+ * activation is written. BAYESIAN only (MT_ERR_UNSUPPORTED otherwise). */
+int mt_dropout_redraw(const mt_net *net, const float *params, int batch, void *ws, size_t ws_bytes, float *v,
+                      float *pi, float *rep, mt_stream_t stream);
 
 /* ---- forward (A5-A7) ----------------------------------------------------------------------
  * Replaces session.run([output_layer_v, output_layer_pi, output_layer_rep], {input_ph: s})

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB = os.environ.get('MANETTE_HIP_LIB') or os.path.join(HERE, 'libmanette_hip.so')  # variant override
 HOST_LIB = os.path.join(HERE, 'libmanette_host.so')
 
-MT_ARCH = {'NIPS': 0, 'NATURE': 1, 'PWYX': 2, 'LSTM': 3}
+MT_ARCH = {'NIPS': 0, 'NATURE': 1, 'PWYX': 2, 'LSTM': 3, 'BAYESIAN': 4}
 MT_ACT = {'relu': 0, 'leaky_relu': 1}
 MT_CLIP = {'ignore': 0, 'global': 1}
 MT_NORM_PARTIALS = 512
@@ -46,7 +46,7 @@ MH_RUNNER_POOLED = 2
 class mt_net_config(C.Structure):
     _fields_ = [('arch', C.c_int32), ('depth', C.c_int32), ('num_actions', C.c_int32),
                 ('num_reps', C.c_int32), ('activation', C.c_int32), ('alpha_leaky', C.c_float),
-                ('softmax_temp', C.c_float)]
+                ('softmax_temp', C.c_float), ('keep_prob', C.c_float)]
 
 
 _P = C.c_void_p
@@ -81,6 +81,8 @@ _HIP_SIGS = {
     'mt_sample': (_I, [_P, _P, _I, _I, _I, C.c_uint64, _I, _P, _P, _P, _P, _P]),
     'mt_returns': (_I, [_P, _P, _P, _P, C.c_double, _I, _I, _P, _P, _P]),
     'mt_loss_backward': (_I, [_P, _P, _P, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    'mt_dropout_redraw': (_I, [_P, _P, _I, _P, _SZ, _P, _P, _P, _P]),
+    'mt_dropout_mask_host': (_I, [C.c_uint64, C.c_uint64, C.c_uint64, _F, _P]),
     'mt_returns_loss_backward': (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, _P,
                                       _F, _P, _P, _P, _P]),
     'mt_returns_loss_backward_boot': (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P,

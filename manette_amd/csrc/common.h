@@ -86,7 +86,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // and the fused rollout heads kernel share it so both draw identical indices. The row is the
 // global env id (local row + row0 = the rank's env offset), so a data-parallel rank draws exactly
 // what a single process owning all envs would draw for the same env.
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
   return z ^ (z >> 31);
@@ -97,6 +97,25 @@ __device__ __forceinline__ void row_uniforms(uint64_t seed, int b, uint64_t c, d
   const uint64_t h2 = mix64(h ^ 0x9e3779b97f4a7c15ULL);
   *ua = (double)(h >> 11) * (1.0 / 9007199254740992.0);
   *ur = (double)(h2 >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// BAYESIAN arch (networks.py:194-204): the dropout mask of tf.nn.dropout(H3, keep_prob), counter-based
+// like the sampler and salted away from its stream. Row base = dropout_base(seed, GLOBAL row, counter);
+// features 4q .. 4q+3 take the four 16-bit fields (low first) of dropout_word(base, q), u = field *
+// 2^-16 (exact in fp32), kept iff the fp32 sum keep_prob + u >= 1 (TF: floor(keep_prob + uniform)).
+// keep_prob == 1: every feature kept. Shared by the kernels (bayes.h) and mt_dropout_mask_host.
+constexpr int kDropF = 256;
+__host__ __device__ __forceinline__ uint64_t dropout_base(uint64_t seed, uint64_t row, uint64_t c) {
+  return mix64(seed ^ mix64((row << 40) ^ c) ^ 0xD6E8FEB86659FD93ULL);
+}
+__host__ __device__ __forceinline__ uint64_t dropout_word(uint64_t base, int q) {
+  return mix64(base + (uint64_t)(q + 1) * 0x9e3779b97f4a7c15ULL);
+}
+__host__ __device__ __forceinline__ bool dropout_keep(uint64_t word, int field, float keep_prob) {
+  if (keep_prob == 1.f) return true;
+  const float u = (float)(uint32_t)((word >> (16 * field)) & 0xffffu) * 1.52587890625e-05f;
+  // (u is exact, so a contraction of the scale into the add rounds the same sum once: no difference)
+  return keep_prob + u >= 1.0f;
 }
 
 __device__ __forceinline__ int draw_index(const float *p, int n, double u) {

@@ -16,6 +16,7 @@
 #include "nips_bwd.h"
 #include "dconv.h"
 #include "nature_bwd.h"
+#include "bayes.h"
 
 namespace mt {
 
@@ -34,6 +35,14 @@ struct NipsArch {  // networks.py:178-192
   static constexpr int FUSED_SLABS = FusedNips<C>::FC_SPLITS;  // inference forward: trunk_fused.h
   static constexpr int FC_ROWS = 0;                         // (the fused trunk has its own dense kernel)
   static constexpr bool LSTM = false;
+  static constexpr int DROP_F = 0;
+};
+// networks.py:194-204: the NIPS trunk, then tf.nn.dropout(fc3) -> fc4 256 -> 256 (bayes.h) under the
+// heads. NIPS geometry, so the fused inference trunk and the fused gray conv backward apply unchanged.
+template <int C>
+struct BayesArch : NipsArch<C> {
+  static constexpr int DROP_F = kDropF;  // the extra stage: dropout over fc3's features + fc4
+  static_assert(NipsArch<C>::F == kDropF, "dropout_fc_kernel is built for 256 features");
 };
 template <int C>
 struct NatureArch {  // networks.py:261-278
@@ -50,6 +59,7 @@ struct NatureArch {  // networks.py:261-278
   // (Breakout isolated step forward 39.5 -> 38.5 us; 4 splits, 256 blocks: slower; profiles/r06fcs)
   static constexpr int FC_SPLITS = 8;
   static constexpr bool LSTM = false;
+  static constexpr int DROP_F = 0;
 };
 template <int C>
 struct PwyxArch {  // networks.py:206-225: SAME convs, 2x2 pools after conv1-3
@@ -64,6 +74,7 @@ struct PwyxArch {  // networks.py:206-225: SAME convs, 2x2 pools after conv1-3
   static constexpr int FC_ROWS = 10;  // dense layer by conv4 rows (row_fc_kernel)
   static constexpr int FC_SPLITS = 8;  // its K-splits: 512 blocks at E = 32 (10: 640), as NATURE's
   static constexpr bool LSTM = false;
+  static constexpr int DROP_F = 0;
 };
 
 template <class Ar, int I>
@@ -128,6 +139,7 @@ struct mt_net {
   size_t off_conv[4];  // weights offset of each conv (biases follow)
   size_t off_fc, off_critic, off_actor, off_rep;
   size_t off_lstm = 0, off_proj = 0;  // LSTM arch: cell kernel (+bias), projection w (+b)
+  size_t off_fc4 = 0;                 // BAYESIAN arch: fc4 weights (biases follow)
 };
 
 namespace mt {
@@ -202,6 +214,13 @@ static void build_layout(mt_net *n) {
   add_convs<Ar>(n, off);
   const float bf = (float)(1.0 / std::sqrt((double)Ar::FLAT));  // networks.py:72-89
   add_pair(n, off, "Network", Ar::FC, {Ar::FLAT, Ar::F}, Ar::F, bf, bf, &n->off_fc);
+  if constexpr (Ar::DROP_F > 0) {
+    // fc4 is built inside a second `with tf.name_scope('Network')`, which TF 1.x uniquifies to
+    // Network_1 (TF's published behaviour; no BAYESIAN checkpoint pins it, as for the LSTM names)
+    const float b4 = (float)(1.0 / std::sqrt((double)Ar::DROP_F));
+    add_named_pair(n, off, "Network_1/fc4/fc4_weights", "Network_1/fc4/fc4_biases", {Ar::DROP_F, Ar::F}, Ar::F, b4,
+                   b4, &n->off_fc4);
+  }
   add_heads<Ar>(n, off);
   n->nparams = align64(off);
   n->F = Ar::F;
@@ -218,6 +237,9 @@ struct WsLayout {
   // the gradient of the conv output (pre-activation after masking; full resolution)
   size_t act[4], pool[4], parg[4], dact[4], fcslab, H, dz, dH, wslab, wslab2, total;
   size_t sync;  // the stacking chains' counters (nature_chain_kernel, stack_conv1_kernel; u32, zero between launches)
+  // BAYESIAN (bayes.h): fc3's output, the mask bytes, the dropped features D, fc4's one-slab product,
+  // fc3's output gradient and the dropout state {seed, row0, counters[B]} (uint64)
+  size_t H3 = 0, mask = 0, D = 0, z4 = 0, dz3 = 0, dstate = 0;
   int fc_splits;
 };
 
@@ -364,6 +386,14 @@ static WsLayout ws_layout(const mt_net *n, int B) {
   L.dH = take((size_t)B * Ar::F);
   L.wslab = take(wslab);
   L.wslab2 = take(wslab);  // ping-pong slab regions of consecutive conv layers (trunk_backward)
+  if constexpr (Ar::DROP_F > 0) {
+    L.H3 = take((size_t)B * Ar::DROP_F);
+    L.mask = take((size_t)B * Ar::DROP_F / 4);  // bytes
+    L.D = take((size_t)B * Ar::DROP_F);
+    L.z4 = take((size_t)B * Ar::F);
+    L.dz3 = take((size_t)B * Ar::DROP_F);
+    L.dstate = take(2 * (size_t)(2 + B));  // uint64 words
+  }
   // the rollout chains' counters (nature_chain_kernel; stack_conv1_kernel), zero between launches
   L.sync = take(nature_stacking<Ar>() ? (size_t)kChainSyncWords * B
                                       : frame_stacking<Ar>() && !Ar::LSTM ? (size_t)stack_conv1_sync_words(B) : 0);
@@ -1330,6 +1360,49 @@ static ActRows act_rows(const mt_net *n, float *ws, const WsLayout &L, const Tra
   return a;
 }
 
+// BAYESIAN: where rows [row0, row0 + B) of an activation workspace keep the stage's values.
+template <class Ar>
+static DropoutFcArgs dropout_args(const mt_net *n, const float *P, int B, const ActRows &A, size_t row0) {
+  DropoutFcArgs d{};
+  d.B = B;
+  d.act = n->cfg.activation;
+  d.alpha = n->cfg.alpha_leaky;
+  d.H3 = A.base + A.L.H3 + row0 * Ar::DROP_F;
+  d.mask = reinterpret_cast<uint8_t *>(A.base + A.L.mask) + row0 * Ar::DROP_F;
+  d.D = A.base + A.L.D + row0 * Ar::DROP_F;
+  d.W4 = P + n->off_fc4;
+  d.keep = n->cfg.keep_prob;
+  return d;
+}
+
+// The end of every forward: the heads kernel finishes the dense layer's S slabs (bias, activation)
+// into H and runs the heads. BAYESIAN: the dropout + fc4 stage (bayes.h) first takes fc3's slabs —
+// state and counters from `ws` (the forward's own workspace), H3 / mask / D into the activation rows —
+// and the heads kernel then finishes fc4's one slab into H = H4.
+template <class Ar>
+static int finish_forward(const mt_net *n, const float *P, int B, float *ws, const WsLayout &L, const ActRows &A,
+                          const TrainRows *tr, int S, float *v, float *pi, float *rep, const SampleArgs *smp,
+                          hipStream_t s) {
+  const float *Wfc = P + n->off_fc;
+  const float *slabs = ws + L.fcslab;
+  const float *bias = Wfc + (size_t)Ar::FLAT * Ar::F;
+  if constexpr (Ar::DROP_F > 0) {
+    DropoutFcArgs d = dropout_args<Ar>(n, P, B, A, tr ? (size_t)tr->row0 : 0);
+    d.slabs = slabs;
+    d.S = S;
+    d.fc_b = bias;
+    d.state = reinterpret_cast<uint64_t *>(ws + L.dstate);
+    d.Z4 = ws + L.z4;
+    MT_TRY(launch_dropout_fc(d, s));
+    slabs = d.Z4;
+    S = 1;
+    bias = d.W4 + (size_t)Ar::DROP_F * Ar::F;
+  }
+  HeadParams hp = head_params(n, P);
+  return launch_heads(B, s, slabs, S, B, bias, n->cfg.activation, n->cfg.alpha_leaky, hp, n->cfg.softmax_temp,
+                      A.base + A.h_off, v, pi, rep, smp ? *smp : SampleArgs{});
+}
+
 template <class Ar>
 static int forward_impl(const mt_net *n, const float *P, const uint8_t *obs, int B, float *ws,
                         float *v, float *pi, float *rep, const SampleArgs *smp, hipStream_t s,
@@ -1347,10 +1420,7 @@ static int forward_impl(const mt_net *n, const float *P, const uint8_t *obs, int
   const float *Wfc = P + n->off_fc;
   MT_TRY((launch_fc<Ar>(flat, B, Wfc, ws + L.fcslab, L.fc_splits, s)));
   if (marks) MT_HIP(hipEventRecord(marks[1], s));
-  HeadParams hp = head_params(n, P);
-  return launch_heads(B, s, ws + L.fcslab, L.fc_splits, B, Wfc + (size_t)Ar::FLAT * Ar::F, n->cfg.activation,
-                      n->cfg.alpha_leaky, hp, n->cfg.softmax_temp, A.base + A.h_off, v, pi, rep,
-                      smp ? *smp : SampleArgs{});
+  return finish_forward<Ar>(n, P, B, ws, L, A, tr, L.fc_splits, v, pi, rep, smp, s);
 }
 
 // Inference forward (rollout steps, bootstrap): the NIPS trunk kernels where the arch has them
@@ -1373,10 +1443,7 @@ static int forward_infer_impl(const mt_net *n, const float *P, const uint8_t *ob
                                  ws + L.fcslab, s)));
     MT_LAUNCHED();
     if (marks) MT_HIP(hipEventRecord(marks[1], s));
-    HeadParams hp = head_params(n, P);
-    return launch_heads(B, s, ws + L.fcslab, Fz::FC_SPLITS, B, Wfc + (size_t)Ar::FLAT * Ar::F, n->cfg.activation,
-                        n->cfg.alpha_leaky, hp, n->cfg.softmax_temp, A.base + A.h_off, v, pi, rep,
-                        smp ? *smp : SampleArgs{});
+    return finish_forward<Ar>(n, P, B, ws, L, A, tr, Fz::FC_SPLITS, v, pi, rep, smp, s);
   } else {
     // (NATURE gray: conv1 stacks, trunk_forward refuses st for the other archs)
     return forward_impl<Ar>(n, P, obs, B, ws, v, pi, rep, smp, s, tr, marks, st);
@@ -1488,17 +1555,37 @@ static int backward_impl(const mt_net *n, const float *P, const uint8_t *obs, in
   const float *flat = layer_out<Ar, K>(ws, L);
   const float *Wfc = P + n->off_fc;
   // dense dW, db: [flat, 1]^T . dH -> grad[(FLAT+1) x F]
-  const auto dw = gemm_job<TileDenseW>(LdColMajor{flat, Ar::FLAT, Ar::FLAT}, LdColMajor{ws + L.dH, Ar::F, -1},
+  // (BAYESIAN: the dense layer's output gradient is dZ3, formed from the loss kernel's dH = dZ4 below)
+  const float *dtop = ws + (Ar::DROP_F > 0 ? L.dz3 : L.dH);
+  const auto dw = gemm_job<TileDenseW>(LdColMajor{flat, Ar::FLAT, Ar::FLAT}, LdColMajor{dtop, Ar::F, -1},
                                        EpStore{grad + n->off_fc, Ar::F}, Ar::FLAT + 1, Ar::F, B, 1);
   const HeadWgradJob hw = head_wgrad_job<Ar>(n, B, ws, L, grad);
   // dense dX: dH . W^T, masked by the last conv's activation (every trunk ends in an unpooled conv)
   static_assert(!pooled<Ar, K>(), "the trunk ends in an unpooled conv (networks.py:178-278)");
-  const auto dx = gemm_job<TileDenseX>(LdRowMajor{ws + L.dH, Ar::F}, LdRowMajor{Wfc, Ar::F},
+  const auto dx = gemm_job<TileDenseX>(LdRowMajor{dtop, Ar::F}, LdRowMajor{Wfc, Ar::F},
                                        EpMasked{ws + L.dact[K], flat, Ar::FLAT, act, al}, B, Ar::FLAT, Ar::F, 1);
-  MT_TRY(launch_group(s, dx, dw, hw));
+  if constexpr (Ar::DROP_F > 0) {
+    // fc4 and the dropout, one grouped launch ahead of the dense layer's: with H = H4 the loss kernel's
+    // dH is dZ4, so gW4, gb4 = [D, 1]^T . dZ4 (the D the last stage stored), dZ3 = (dZ4 . W4^T) (.) m /
+    // keep (.) act'(H3) (EpDropMasked: the stored mask bytes and H3's branch), and the head dW as ever.
+    // The dense / head gradients therefore complete one launch later: this backward is not bucketed.
+    constexpr int DF = Ar::DROP_F;
+    const float *W4 = P + n->off_fc4;
+    const auto dw4 = gemm_job<TileDenseW>(LdColMajor{ws + L.D, DF, DF}, LdColMajor{ws + L.dH, Ar::F, -1},
+                                          EpStore{grad + n->off_fc4, Ar::F}, DF + 1, Ar::F, B, 1);
+    const auto dx4 = gemm_job<TileDenseX>(
+        LdRowMajor{ws + L.dH, Ar::F}, LdRowMajor{W4, Ar::F},
+        EpDropMasked{ws + L.dz3, ws + L.H3, reinterpret_cast<const uint8_t *>(ws + L.mask), DF, act, al,
+                     n->cfg.keep_prob},
+        B, DF, Ar::F, 1);
+    MT_TRY(launch_group(s, dx4, dw4, hw));
+    MT_TRY(launch_group(s, dx, dw));
+  } else {
+    MT_TRY(launch_group(s, dx, dw, hw));
+  }
   // the data-parallel split point: every dense / head gradient is complete after this launch
   // (mt_net_backward_bucket_launches; paac._bucketed_update all-reduces that bucket next)
-  if (g_win_on && g_win_index != kDenseBucketLaunches) {
+  if (Ar::DROP_F == 0 && g_win_on && g_win_index != kDenseBucketLaunches) {
     set_error("backward: the dense / head gradients completed after launch %d, not %d", g_win_index,
               kDenseBucketLaunches);
     return MT_ERR_UNSUPPORTED;
@@ -1528,6 +1615,8 @@ using namespace mt;
     else if (arch_ == MT_ARCH_PWYX && d_ == 3) { using Ar = PwyxArch<12>; __VA_ARGS__; }    \
     else if (arch_ == MT_ARCH_LSTM && d_ == 1) { using Ar = LstmArch<4>; __VA_ARGS__; }     \
     else if (arch_ == MT_ARCH_LSTM && d_ == 3) { using Ar = LstmArch<12>; __VA_ARGS__; }    \
+    else if (arch_ == MT_ARCH_BAYESIAN && d_ == 1) { using Ar = BayesArch<4>; __VA_ARGS__; } \
+    else if (arch_ == MT_ARCH_BAYESIAN && d_ == 3) { using Ar = BayesArch<12>; __VA_ARGS__; } \
     else { set_error("arch %d depth %d not built", arch_, d_); return MT_ERR_UNSUPPORTED; } \
   } while (0)
 
@@ -1538,6 +1627,9 @@ extern "C" int mt_net_create(const mt_net_config *cfg, mt_net **out) {
   MT_CHECK_ARG(cfg->num_reps >= 1 && cfg->num_reps <= 31, "num_reps out of range [1,31]");
   MT_CHECK_ARG(cfg->activation == MT_ACT_RELU || cfg->activation == MT_ACT_LEAKY, "bad activation");
   MT_CHECK_ARG(cfg->softmax_temp > 0.f, "softmax_temp must be > 0");
+  // (NaN fails both comparisons; the other archs ignore the field)
+  MT_CHECK_ARG(cfg->arch != MT_ARCH_BAYESIAN || (cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f),
+               "keep_prob must be in (0, 1] for the BAYESIAN arch");
   mt_net *n = new mt_net();
   n->cfg = *cfg;
   n->C = 4 * cfg->depth;
@@ -1551,6 +1643,8 @@ extern "C" int mt_net_create(const mt_net_config *cfg, mt_net **out) {
   else if (arch == MT_ARCH_PWYX && d == 3) build_layout<PwyxArch<12>>(n);
   else if (arch == MT_ARCH_LSTM && d == 1) build_layout_lstm<LstmArch<4>>(n);
   else if (arch == MT_ARCH_LSTM && d == 3) build_layout_lstm<LstmArch<12>>(n);
+  else if (arch == MT_ARCH_BAYESIAN && d == 1) build_layout<BayesArch<4>>(n);
+  else if (arch == MT_ARCH_BAYESIAN && d == 3) build_layout<BayesArch<12>>(n);
   else {
     delete n;
     set_error("arch %d not built into this library", arch);
@@ -1616,6 +1710,9 @@ extern "C" int mt_net_backward_bucket_launches(const mt_net *net, int *launches)
     if constexpr (Ar::LSTM) {
       set_error("the LSTM backward is not bucketed");
       return MT_ERR_UNSUPPORTED;
+    } else if constexpr (Ar::DROP_F > 0) {
+      set_error("the BAYESIAN backward is not bucketed (its dense gradients complete one launch later)");
+      return MT_ERR_UNSUPPORTED;
     } else {
       *launches = kDenseBucketLaunches;  // backward_impl: loss | dense dX + dense dW + head dW | convs
     }
@@ -1640,6 +1737,16 @@ static int ws_region(const WsLayout &L, int kind, int layer, size_t rows, size_t
     *offset = L.H * sizeof(float);
     *bytes = rows * Ar::F * sizeof(float);
     return MT_OK;
+  }
+  if (kind >= 5) {  // BAYESIAN: the mask bytes, H3, the dropout state (bayes.h)
+    if constexpr (Ar::DROP_F > 0) {
+      *offset = (kind == 5 ? L.mask : kind == 6 ? L.H3 : L.dstate) * sizeof(float);
+      *bytes = kind == 5 ? rows * Ar::DROP_F : kind == 6 ? rows * Ar::DROP_F * sizeof(float) : (2 + rows) * 8;
+      return MT_OK;
+    } else {
+      set_error("regions 5-7 belong to the BAYESIAN arch");
+      return MT_ERR_ARG;
+    }
   }
   if constexpr (I < Ar::NCONV) {
     if (layer != I) return ws_region<Ar, I + 1>(L, kind, layer, rows, offset, bytes);
@@ -1683,8 +1790,9 @@ static int ws_region_frames(const mt_net *net, int E, int T, int kind, int layer
 extern "C" int mt_net_workspace_region(const mt_net *net, int layout, int a, int b, int kind, int layer,
                                        size_t *offset, size_t *bytes) {
   MT_CHECK_ARG(net && offset && bytes, "null argument");
-  MT_CHECK_ARG(a >= 1 && (layout != 1 || b >= 1) && kind >= 0 && kind <= 4, "bad sizes or kind");
-  MT_CHECK_ARG(kind != 4 || layout == 0, "the counter region (kind 4) is in the layout-0 workspace");
+  MT_CHECK_ARG(a >= 1 && (layout != 1 || b >= 1) && kind >= 0 && kind <= 7, "bad sizes or kind");
+  MT_CHECK_ARG(kind < 4 || layout == 0,
+               "the counter region (kind 4) and the dropout regions (5-7) are in the layout-0 workspace");
   MT_ARCH_SWITCH(net, {
     if (layout == 0) {
       if constexpr (Ar::LSTM) {
@@ -1781,6 +1889,9 @@ extern "C" int mt_forward_trunk_stacking(const mt_net *net, const float *params,
     }
     if constexpr (Ar::LSTM) {
       set_error("stacking trunk: the NIPS, gray NATURE and PWYX archs (the LSTM steps: mt_lstm_step_forward)");
+      return MT_ERR_UNSUPPORTED;
+    } else if constexpr (Ar::DROP_F > 0) {
+      set_error("stacking trunk: not built for the BAYESIAN arch (call mt_forward_infer on the stacked state)");
       return MT_ERR_UNSUPPORTED;
     } else {
       return trunk_infer_impl<Ar>(net, params, out, batch, (float *)ws, (hipStream_t)stream, &st);
@@ -1884,6 +1995,46 @@ extern "C" int mt_loss_backward(const mt_net *net, const float *params, const ui
   return MT_OK;
 }
 
+extern "C" int mt_dropout_redraw(const mt_net *net, const float *params, int batch, void *ws, size_t ws_bytes,
+                                 float *v, float *pi, float *rep, mt_stream_t stream) {
+  MT_CHECK_ARG(net && params && ws && v && pi && rep, "null argument");
+  MT_CHECK_ARG(batch >= 1, "batch must be >= 1");
+  MT_ARCH_SWITCH(net, {
+    if constexpr (Ar::DROP_F == 0) {
+      set_error("mt_dropout_redraw: the BAYESIAN arch only");
+      return MT_ERR_UNSUPPORTED;
+    } else {
+      const WsLayout L = ws_layout<Ar>(net, batch);
+      if (ws_bytes < L.total * sizeof(float)) {
+        set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
+        return MT_ERR_WORKSPACE;
+      }
+      // the forward stage's kernel with the slab sum replaced by a load of the stored H3: fresh masks
+      // -> D -> Z4 -> heads; H3 and the conv activations are only read
+      float *w = (float *)ws;
+      const ActRows A{w, L, L.H};
+      DropoutFcArgs d = dropout_args<Ar>(net, params, batch, A, 0);
+      d.state = reinterpret_cast<uint64_t *>(w + L.dstate);
+      d.Z4 = w + L.z4;
+      MT_TRY(launch_dropout_fc(d, (hipStream_t)stream));
+      HeadParams hp = head_params(net, params);
+      return launch_heads(batch, (hipStream_t)stream, d.Z4, 1, batch, d.W4 + (size_t)Ar::DROP_F * Ar::F,
+                          net->cfg.activation, net->cfg.alpha_leaky, hp, net->cfg.softmax_temp, w + L.H, v, pi, rep,
+                          SampleArgs{});
+    }
+  });
+  return MT_OK;
+}
+
+extern "C" int mt_dropout_mask_host(uint64_t seed, uint64_t global_row, uint64_t counter, float keep_prob,
+                                    uint8_t *out) {
+  MT_CHECK_ARG(out, "null argument");
+  MT_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "keep_prob must be in (0, 1]");
+  const uint64_t base = dropout_base(seed, global_row, counter);
+  for (int f = 0; f < kDropF; ++f) out[f] = dropout_keep(dropout_word(base, f >> 2), f & 3, keep_prob) ? 1 : 0;
+  return MT_OK;
+}
+
 extern "C" int mt_returns_loss_backward(const mt_net *net, const float *params, const uint8_t *obs, int T, int E,
                                         void *ws, size_t ws_bytes, const float *pi, const float *rep,
                                         const float *values, const int32_t *a_idx, const int32_t *r_idx,
@@ -1898,6 +2049,11 @@ extern "C" int mt_returns_loss_backward(const mt_net *net, const float *params, 
   MT_ARCH_SWITCH(net, {
     if constexpr (Ar::LSTM) {
       set_error("mt_returns_loss_backward: the LSTM arch trains through mt_lstm_frames_backward");
+      return MT_ERR_UNSUPPORTED;
+    } else if constexpr (Ar::DROP_F > 0) {
+      // one `values` array cannot be both the rollout's v (the advantage) and the redrawn v (the critic)
+      set_error("mt_returns_loss_backward: the BAYESIAN arch trains through mt_returns, mt_dropout_redraw and "
+                "mt_loss_backward");
       return MT_ERR_UNSUPPORTED;
     } else {
       const WsLayout L = ws_layout<Ar>(net, batch);
@@ -1939,6 +2095,10 @@ extern "C" int mt_returns_loss_backward_boot(const mt_net *net, const float *par
   MT_ARCH_SWITCH(net, {
     if constexpr (Ar::LSTM) {
       set_error("mt_returns_loss_backward_boot: the LSTM arch trains through mt_lstm_frames_backward");
+      return MT_ERR_UNSUPPORTED;
+    } else if constexpr (Ar::DROP_F > 0) {
+      set_error("mt_returns_loss_backward_boot: the BAYESIAN arch trains through mt_returns, mt_dropout_redraw "
+                "and mt_loss_backward");
       return MT_ERR_UNSUPPORTED;
     } else {
       const WsLayout L = ws_layout<Ar>(net, batch);

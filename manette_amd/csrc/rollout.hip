@@ -99,6 +99,15 @@ extern "C" int mt_rollout_create(const mt_net *net, int E, int T, void *runner, 
                                  mt_rollout **out) {
   MT_CHECK_ARG(net && runner && book && buffers && out, "null argument");
   MT_CHECK_ARG(E >= 1 && T >= 1, "E and T must be >= 1");
+  {
+    mt_net_config c0;
+    MT_CHECK_ARG(mt_net_get_config(net, &c0) == MT_OK, "bad net");
+    if (c0.arch == MT_ARCH_BAYESIAN) {  // (refused before any buffer is touched)
+      set_error("mt_rollout_create: the native macro-step is not built for the BAYESIAN arch (step with "
+                "mt_forward_rows + mt_sample, update with mt_returns, mt_dropout_redraw and mt_loss_backward)");
+      return MT_ERR_UNSUPPORTED;
+    }
+  }
   const mt_rollout_buffers &b = *buffers;
   const bool ip = (b.flags & MT_ROLLOUT_IN_PLACE) != 0;
   const bool zc = ip || (b.flags & MT_ROLLOUT_ZERO_COPY) != 0;

@@ -60,9 +60,13 @@ class DeviceNetwork(object):
         self.clip_type = _lib.MT_CLIP[clip_type]
         self.decay = float(conf.get('alpha', 0.99))
         self.eps = float(conf.get('e', 0.1))
+        if self.arch not in _lib.MT_ARCH:
+            raise ValueError('arch %r not supported (valid: %s)' % (self.arch, ', '.join(sorted(_lib.MT_ARCH))))
+        self.bayesian = self.arch == 'BAYESIAN'
+        self.keep_prob = float(conf.get('keep_percentage', 1.0))  # networks.py:194-204 (BAYESIAN only)
         cfg = _lib.mt_net_config(_lib.MT_ARCH[self.arch], self.depth, self.num_actions,
                                  self.num_reps, _lib.MT_ACT[conf.get('activation', 'relu')],
-                                 float(conf.get('alpha_leaky_relu', 0.1)), self.temp)
+                                 float(conf.get('alpha_leaky_relu', 0.1)), self.temp, self.keep_prob)
         lib = _lib.hip()
         h = C.c_void_p()
         check(lib.mt_net_create(C.byref(cfg), C.byref(h)), 'mt_net_create')
@@ -159,7 +163,8 @@ class DeviceNetwork(object):
         (mt_net_workspace_region): {'convK': (output, argmax)} — the conv layer's post-activation
         output [rows, H', W', C] fp32 (a pooled layer's pooled map; its sign is the ReLU branch) and,
         for a pooled layer, the max-pool argmax [rows, H', W', C] uint8 (window position 0..3 =
-        2 * row + col) else None — and 'H': the dense output [rows', F]. layout 0 = a forward of `a`
+        2 * row + col) else None — and 'H': the dense output [rows', F] (BAYESIAN: 'H' = H4, the
+        features the heads read, plus 'H3' = fc3's output and 'mask' = the dropout bytes). layout 0 = a forward of `a`
         rows; 1 = the LSTM frame store of E = a, T = b (conv rows = its 1 + (T + 5) E frames, H rows =
         its (T + 1) E windows); 2 = an LSTM forward of `a` windows (conv rows = 5 a frames)."""
         lib = _lib.hip()
@@ -186,7 +191,51 @@ class DeviceNetwork(object):
             out[name.split('/')[1]] = (y, arg)
         off, n = region(2, 0)
         out['H'] = raw[off:off + n].view(np.float32).reshape(hrows, -1).copy()
+        if self.bayesian:  # 'H' is H4 (the features the heads read); fc3's output and the mask beside it
+            off, n = region(6, 0)
+            out['H3'] = raw[off:off + n].view(np.float32).reshape(hrows, -1).copy()
+            off, n = region(5, 0)
+            out['mask'] = raw[off:off + n].reshape(hrows, -1).copy()
         return out
+
+    # ---- BAYESIAN dropout (include/manette_hip.h) ----------------------------------------------
+    def _ws_region(self, ws, batch, kind):
+        off, n = C.c_size_t(), C.c_size_t()
+        check(_lib.hip().mt_net_workspace_region(self._h, 0, int(batch), 0, int(kind), 0, C.byref(off), C.byref(n)),
+              'mt_net_workspace_region')
+        return ws[off.value:off.value + n.value]
+
+    def set_dropout_state(self, ws, seed, row0, batch=None):
+        """Seed the dropout stream of one call site: ws is a workspace key (with `batch` rows, created
+        if need be) or a workspace tensor of `batch` rows. Writes {seed, row0} of region 7 and zeroes
+        the per-row counters; row b's masks are then keyed on (seed, row0 + b, calls so far)."""
+        if not torch.is_tensor(ws):
+            key = ws
+            batch = key if batch is None else batch  # (the default workspace key is its batch size)
+            ws = self.workspace(int(batch), key)
+        st = self._ws_region(ws, int(batch), 7).view(torch.int64)
+        st.zero_()
+        m = (1 << 63)
+        st[:2] = torch.tensor([((int(v) & (2 * m - 1)) ^ m) - m for v in (seed, row0)], dtype=torch.int64)
+
+    def dropout_state(self, ws, batch):
+        """(seed, row0, counters [batch]) of a workspace's dropout state, as numpy uint64."""
+        st = self._ws_region(ws, int(batch), 7).cpu().numpy().view(np.uint64)
+        return int(st[0]), int(st[1]), st[2:].copy()
+
+    def dropout_mask(self, ws, batch):
+        """The mask bytes [batch][256] (0 / 1) the last stage left in ws."""
+        return self._ws_region(ws, int(batch), 5).cpu().numpy().reshape(int(batch), -1).copy()
+
+    def dropout_redraw(self, batch, out, ws_key=None):
+        """mt_dropout_redraw: the train step's fresh mask over the H3 a forward left in the workspace:
+        new masks -> D -> fc4 -> heads into out = (v, pi, rep); the mask and H4 stay for loss_backward."""
+        B = int(batch)
+        ws = self.workspace(B, ws_key)
+        v, pi, rep = out
+        check(_lib.hip().mt_dropout_redraw(self._h, _ptr(self.params), B, _ptr(ws), ws.numel(), _ptr(v), _ptr(pi),
+                                           _ptr(rep), _stream()), 'mt_dropout_redraw')
+        return v, pi, rep
 
     # ---- compute -----------------------------------------------------------------------------
     def forward(self, obs, batch=None, out=None, ws_key=None, infer=False):

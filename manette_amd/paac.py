@@ -54,6 +54,9 @@ class PAACLearner(ActorLearner):
         self.pin_threads = getattr(args, 'pin_threads', 'auto')
         self.total_repetitions = args.nb_choices
         self.lstm_bool = (args.arch == 'LSTM')
+        # dropout in every forward, a fresh mask in the train step (networks.py:194-204): Python step(),
+        # eager update with mt_dropout_redraw (update()), never the native macro-step or a captured update
+        self.bayes_bool = (args.arch == 'BAYESIAN')
         self.tab_rep = explo_policy.tab_rep
         self.runner_kind = getattr(args, 'runner', 'native')
         self.sampling = getattr(args, 'sampling', 'host')
@@ -118,6 +121,19 @@ class PAACLearner(ActorLearner):
         self.rep_all = torch.zeros(T + 1, E, self.total_repetitions, dtype=torch.float32, device=dev)
         self.train_ws = None if self.lstm_bool else self.network.workspace(T * E, 'train')
         self.v_boot = torch.zeros(E, dtype=torch.float32, device=dev)
+        self.sample_seed = (self.seed * 1000003 + 1) & 0xffffffffffff  # rank-independent: rows are global
+        if self.bayes_bool:
+            # the train step's own outputs under its fresh mask (v', pi', rep'): the loss reads these,
+            # the advantage keeps the rollout's values (paac.py:219-231, policy_v_network.py:25-74)
+            self.v_upd = torch.zeros(T * E, dtype=torch.float32, device=dev)
+            self.pi_upd = torch.zeros(T * E, self.num_actions, dtype=torch.float32, device=dev)
+            self.rep_upd = torch.zeros(T * E, self.total_repetitions, dtype=torch.float32, device=dev)
+            # one dropout stream per call site and global row: the rollout workspace (steps + bootstrap)
+            # keyed on the global env id, the train workspace on the global train row under a salted seed
+            self.network.set_dropout_state('rollout', self.sample_seed, self.env_offset, batch=E)
+            self.network.set_dropout_state(self.train_ws, self.sample_seed ^ 0x7452414e5f575321,
+                                           T * self.env_offset, batch=T * E)
+            self._native_note = False
         self.loss_terms = torch.zeros(T * E, 4, dtype=torch.float32, device=dev)
         self.counters = torch.zeros(E, dtype=torch.int64, device=dev)
         pin = dict(pin_memory=True)
@@ -143,7 +159,6 @@ class PAACLearner(ActorLearner):
         self.runners = None
         self.placement = None    # host-thread plan of the native runner (_plan_threads)
         self.profile = None      # name -> [(start_event, end_event)] when profiling (bench.py)
-        self.sample_seed = (self.seed * 1000003 + 1) & 0xffffffffffff  # rank-independent: rows are global
         # replay the update as hipGraph(s) from the second update on (native pipelined step)
         self.use_update_graph = bool(getattr(args, 'update_graph', True))
         self._graphs = None
@@ -194,7 +209,9 @@ class PAACLearner(ActorLearner):
             else:
                 # only the 84 screen rows the nearest resize reads are staged (PCIe); zero_copy:
                 # kernels read env e's pushes in place at staging slots 4e..
-                fixed = self.sampling == 'device' and self.staging in ('zero_copy', 'pooled', 'resized')
+                # (fixed slots serve the native step's in-place reads; BAYESIAN steps in Python: compact staging)
+                fixed = self.sampling == 'device' and self.staging in ('zero_copy', 'pooled', 'resized') \
+                    and not self.bayes_bool
                 self.runners = NativeRunners(bank, self.workers, self.tab_rep, row_select=ROW_LUT,
                                              fixed_slots=fixed, pooled=self.staging == 'pooled',
                                              resized=self.staging == 'resized', col_lut=COL_LUT)
@@ -206,7 +223,11 @@ class PAACLearner(ActorLearner):
             if self.placement['pinned'] or self.placement['sliced']:  # ('slice': no worker cpus, the spin only)
                 self.runners.set_threads(self.placement['worker_cpus'], self.placement['spin_us'])
                 placement.apply_main(self.placement)
-            if self.sampling == 'device':
+            if self.sampling == 'device' and self.bayes_bool:
+                if not self._native_note:
+                    logging.info('BAYESIAN: no native macro-step; --sampling device runs the Python step with mt_sample')
+                    self._native_note = True
+            elif self.sampling == 'device':
                 self._make_native_step()
         else:
             emus = [self.environment_creator.create_environment(i) for i in range(E)]
@@ -406,7 +427,11 @@ class PAACLearner(ActorLearner):
         fixed buffers (the LR is read from pinned host memory, the returns kernel reads the
         rollout's rewards / masks in place), so from the second update on it is replayed as one
         or two hipGraphs (mt_graph_*; split around the all_reduce when world > 1): one launch
-        instead of a dozen, and no host launch gaps between the backward's kernels."""
+        instead of a dozen, and no host launch gaps between the backward's kernels.
+
+        BAYESIAN (always eager): bootstrap forward, mt_returns on the rollout's values, the train
+        step's fresh mask (mt_dropout_redraw -> v', pi', rep'), mt_loss_backward on those with the
+        rollout's advantage, [whole-gradient all-reduce], mt_grad_sumsq + clip + RMSProp."""
         self.book.drain()
         lr = self.get_lr()
         if self._update_in_rollout:  # the rollout's last step stored lr and launched the update graph
@@ -441,7 +466,7 @@ class PAACLearner(ActorLearner):
         self._update_backward()
         if self.dp:
             grad = self.network.grad
-            if not self.lstm_bool and os.environ.get('MT_DP_BUCKETS', '1') != '0':
+            if not self.lstm_bool and not self.bayes_bool and os.environ.get('MT_DP_BUCKETS', '1') != '0':
                 # the captured update's two bucket sums, in its order: every size the graph will
                 # replay has run (and connected its RCCL channels) before the capture
                 off = self._dense_offset()
@@ -481,7 +506,7 @@ class PAACLearner(ActorLearner):
         self._launch_graph(g3, s)             # global-norm partials + clip + RMSProp
 
     def _graph_ok(self):
-        return (self.use_update_graph and self.profile is None
+        return (self.use_update_graph and self.profile is None and not self.bayes_bool
                 and self.native_step is not None and self.boot_in_rollout)
 
     def _update_backward(self):
@@ -492,7 +517,9 @@ class PAACLearner(ActorLearner):
             self._lstm_forward(T, self.v_boot)
         elif not self.lstm_bool and not boot_done:
             net.forward(self.states[T], E, out=(self.v_boot, self.pi_roll, self.rep_roll), ws_key='rollout', infer=True)
-        if self.lstm_bool:
+        if self.lstm_bool or self.bayes_bool:
+            # (BAYESIAN: y and adv = y - the ROLLOUT's values, under the rollout's masks; the fused
+            # returns + loss launch would feed one `values` to both the advantage and the critic)
             devnet.returns(self.rm_h_dev, self.rm_h_dev + 4 * T * E, self.values, self.v_boot, self.gamma, self.y,
                            self.adv)
             end = self._mark('train_pass')
@@ -524,13 +551,21 @@ class PAACLearner(ActorLearner):
         # the rollout's forwards already left every row's activations in the train workspace
         # (mt_forward_rows, row t*E + e as paac.py:236)
         obs = self.states[:T].reshape(N, 84, 84, self.C)
+        if self.bayes_bool:
+            # the train step's fresh mask over the rollout's H3 rows: v', pi', rep' and the mask / H4 the
+            # backward reads (each call draws the next mask: not idempotent, as the reference's is not)
+            out = net.dropout_redraw(N, (self.v_upd, self.pi_upd, self.rep_upd), ws_key='train')
+            net.loss_backward(obs, N, out[0], out[1], out[2], self.idx[0].view(N), self.idx[1].view(N),
+                              self.y.view(N), self.adv.view(N), loss_terms=self.loss_terms, ws_key='train')
+            return
         self.network.loss_backward(obs, N, self.values.view(N), self.pi_all[:T].reshape(N, -1),
                                    self.rep_all[:T].reshape(N, -1), self.idx[0].view(N), self.idx[1].view(N),
                                    self.y.view(N), self.adv.view(N), loss_terms=self.loss_terms, ws_key='train')
 
     def _update_apply(self):
         T = self.max_local_steps
-        self.network.apply_gradients(self.grad_scale, partials_ready=not self.dp)
+        # (the LSTM / fused-returns backwards leave the norm partials; BAYESIAN's mt_loss_backward does not)
+        self.network.apply_gradients(self.grad_scale, partials_ready=not self.dp and not self.bayes_bool)
         if self.lstm_bool:  # the next rollout's slots 0..4 = s_{T-4} .. s_T; windows carry over
             if T >= 5:
                 self.slots[0:5].copy_(self.slots[T:T + 5])

@@ -84,7 +84,10 @@ def run(args, max_macro_steps=None):
         network.set_variables({k: v for k, v in t.items() if not k.endswith((SLOT_MS, SLOT_MOM))})
 
     n = args.test_count
-    environments = [env_creator.create_environment(i) for i in range(n)]
+    if args.arch == 'BAYESIAN':
+        # dropout stays on in evaluation, as in the reference (no training switch, networks.py:194-204)
+        network.set_dropout_state('test', int(getattr(args, 'seed', 0)), 0, batch=n)
+    environments =[env_creator.create_environment(i) for i in range(n)]
     states = np.asarray([e.get_initial_state() for e in environments])
     if args.noops != 0:
         for i, environment in enumerate(environments):
