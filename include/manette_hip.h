@@ -243,6 +243,53 @@ int mt_sample(const float *pi, const float *rep, int batch, int num_actions, int
               uint64_t seed, int row0, uint64_t *counters, int32_t *a_idx, int32_t *r_idx, int32_t *pair,
               mt_stream_t stream);
 
+/* ---- device exploration policy (the three choosers of exploration_policy.py:78-116) ----------
+ * mt_sample draws multinomially; a policy selects e_greedy_choose with its annealing
+ * (exploration_policy.py:73-76, :101-108) or argmax_choose (:98-99) instead, in mt_sample_policy and
+ * in the draw fused into the rollout's heads kernel (mt_rollout_set_policy). A zero-filled mt_policy
+ * is mt_sample's multinomial draw, bit for bit.
+ *
+ * Draw rule of one row (global_row = row0 + row, counter = counters[row] before the call); every mode
+ * consumes one counter value per row per call:
+ *   uniforms   h  = mix64(seed ^ mix64((global_row << 40) ^ counter))      (mix64: splitmix64's finaliser,
+ *              h2 = mix64(h ^ 0x9e3779b97f4a7c15)                           spelled out above)
+ *              ua = (h >> 11) * 2^-53,  ur = (h2 >> 11) * 2^-53            (doubles in [0, 1))
+ *   epsilon    g = (double)(counter * rows_per_call), a uint64 product      (the reference's global_step:
+ *              not annealed: eps = epsilon                                  it grows by the rows of a
+ *              annealed:     eps = g <= annealing_steps                     choose call, and the row's
+ *                                  ? epsilon - (g * epsilon / annealing_steps) : 0.0   counter = earlier calls)
+ *              in double, in this operation order (a product, a quotient, a difference: nothing a
+ *              compiler can contract), so host, device and numpy agree bit for bit. Epsilon needs no
+ *              host word, survives graph replay, and a data-parallel shard anneals as the union would.
+ *   MULTINOMIAL  inverse CDF on (p - epsneg) as mt_sample: action from ua, repetition from ur.
+ *   EGREEDY    head of size n with uniform u (action: ua, repetition: ur, independently — the
+ *              reference calls e_greedy_choose once per head):
+ *                u < eps:   min(n - 1, (int)floor((u / eps) * n))   (u / eps is uniform on [0, 1) given
+ *                           u < eps: no second hash)
+ *                otherwise: the first maximum.
+ *   ARGMAX     the first maximum in index order, as np.argmax: a NaN entry counts as the maximum and
+ *              the first NaN wins (EGREEDY with eps = 0).
+ * Whatever the inputs, an index is in [0, n). num_reps == 1: the repetition index is 0 in every mode. */
+enum { MT_POLICY_MULTINOMIAL = 0, MT_POLICY_EGREEDY = 1, MT_POLICY_ARGMAX = 2 };
+typedef struct {
+  int32_t mode;            /* MT_POLICY_* */
+  int32_t annealed;        /* EGREEDY: 0 = constant epsilon, 1 = annealed from the row's draw counter */
+  double epsilon;          /* initial epsilon, in [0, 1] */
+  double annealing_steps;  /* > 0 when annealed */
+  int64_t rows_per_call;   /* what the reference's global_step grows by per choose call (>= 1) */
+} mt_policy;
+
+/* mt_sample under a policy (NULL = multinomial). MT_ERR_ARG, before any launch, for a mode outside
+ * 0..2, an epsilon outside [0, 1] or NaN, annealing_steps <= 0 (or NaN) when annealed, or
+ * rows_per_call < 1 in a mode other than MULTINOMIAL (the zero-filled policy stays valid). */
+int mt_sample_policy(const mt_policy *policy, const float *pi, const float *rep, int batch, int num_actions,
+                     int num_reps, uint64_t seed, int row0, uint64_t *counters, int32_t *a_idx, int32_t *r_idx,
+                     int32_t *pair, mt_stream_t stream);
+/* Host restatement of the rule above for one row, all three modes (pi, rep: HOST pointers); needs no
+ * GPU. The kernels are pinned against it. */
+int mt_policy_draw_host(const mt_policy *policy, uint64_t seed, uint64_t global_row, uint64_t counter,
+                        const float *pi, int num_actions, const float *rep, int num_reps, int32_t *a, int32_t *r);
+
 /* ---- n-step return / advantage scan (A9) ---------------------------------------------------
  * Replaces paac.py:219-231 (+ flatten :237-238). rewards/masks/values: [T][E] fp32,
  * v_boot: [E] (V(s_T)). Writes y, adv: [T][E] fp32 (row t*E+e). Arithmetic follows the
@@ -448,6 +495,11 @@ int mt_rollout_step(mt_rollout *ro, const float *params, int t, int64_t *global_
 /* The whole rollout: mt_rollout_step for t = 0 .. T-1 in one call (paac.py:140-205 without a
  * return to the caller between macro-steps). */
 int mt_rollout_run(mt_rollout *ro, const float *params, int64_t *global_step, mt_stream_t stream);
+/* The exploration policy of the draw fused into every step's heads kernel (mt_policy above; NULL =
+ * multinomial, the default), every arch the rollout serves, LSTM included. Checked as mt_sample_policy
+ * checks it. Accepted only before the rollout's first mt_rollout_step — MT_ERR_ARG after it: the
+ * replayed rollout graph bakes the kernel arguments in. */
+int mt_rollout_set_policy(mt_rollout *ro, const mt_policy *policy);
 /* Host wall-clock microseconds accumulated by mt_rollout_step, per phase: [0] launch + wait
  * for the sampled indices, [1] emulator step, [2] bookkeeping, [3] upload + preprocess
  * enqueue, [4] number of steps. reset != 0 zeroes the counters. */

@@ -49,6 +49,15 @@ class mt_net_config(C.Structure):
                 ('softmax_temp', C.c_float), ('keep_prob', C.c_float)]
 
 
+MT_POLICY = {'multinomial': 0, 'egreedy': 1, 'argmax': 2}
+
+
+class mt_policy(C.Structure):
+    """Exploration policy of the device draw (include/manette_hip.h); all zeros = multinomial."""
+    _fields_ = [('mode', C.c_int32), ('annealed', C.c_int32), ('epsilon', C.c_double),
+                ('annealing_steps', C.c_double), ('rows_per_call', C.c_int64)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -79,6 +88,10 @@ _HIP_SIGS = {
     'mt_forward_trunk_stacking': (_I, [_P, _P, _P, _P, _P, C.c_uint32, _P, _I, _P, _SZ, _P, _P]),
     'mt_forward_infer': (_I, [_P, _P, _P, _I, _P, _SZ, _P, _P, _P, _P]),
     'mt_sample': (_I, [_P, _P, _I, _I, _I, C.c_uint64, _I, _P, _P, _P, _P, _P]),
+    'mt_sample_policy': (_I, [C.POINTER(mt_policy), _P, _P, _I, _I, _I, C.c_uint64, _I, _P, _P, _P, _P, _P]),
+    'mt_policy_draw_host': (_I, [C.POINTER(mt_policy), C.c_uint64, C.c_uint64, C.c_uint64, _P, _I, _P, _I,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'mt_rollout_set_policy': (_I, [_P, C.POINTER(mt_policy)]),
     'mt_returns': (_I, [_P, _P, _P, _P, C.c_double, _I, _I, _P, _P, _P]),
     'mt_loss_backward': (_I, [_P, _P, _P, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     'mt_dropout_redraw': (_I, [_P, _P, _I, _P, _SZ, _P, _P, _P, _P]),

@@ -92,8 +92,8 @@ __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 
-__device__ __forceinline__ void row_uniforms(uint64_t seed, int b, uint64_t c, double *ua, double *ur) {
-  const uint64_t h = mix64(seed ^ mix64(((uint64_t)b << 40) ^ c));
+__host__ __device__ __forceinline__ void row_uniforms(uint64_t seed, uint64_t b, uint64_t c, double *ua, double *ur) {
+  const uint64_t h = mix64(seed ^ mix64((b << 40) ^ c));
   const uint64_t h2 = mix64(h ^ 0x9e3779b97f4a7c15ULL);
   *ua = (double)(h >> 11) * (1.0 / 9007199254740992.0);
   *ur = (double)(h2 >> 11) * (1.0 / 9007199254740992.0);
@@ -118,7 +118,7 @@ __host__ __device__ __forceinline__ bool dropout_keep(uint64_t word, int field, 
   return keep_prob + u >= 1.0f;
 }
 
-__device__ __forceinline__ int draw_index(const float *p, int n, double u) {
+__host__ __device__ __forceinline__ int draw_index(const float *p, int n, double u) {
   const double epsneg = 5.9604644775390625e-08;  // np.finfo(np.float32).epsneg
   double cum = 0.0;
   for (int j = 0; j < n - 1; ++j) {
@@ -128,15 +128,63 @@ __device__ __forceinline__ int draw_index(const float *p, int n, double u) {
   return n - 1;
 }
 
-__device__ __forceinline__ void sample_row(const float *pa, int A, const float *pr, int R, uint64_t seed,
-                                           int b, int row0, uint64_t *counters, int *a, int *r) {
+// Exploration policy (include/manette_hip.h, mt_policy: the rule is written out there). Epsilon of the
+// call that reads draw counter c (exploration_policy.py:73-76, in double, same operation order: a
+// product, a quotient, a difference — nothing to contract into an fma). ARGMAX is EGREEDY at eps = 0.
+__host__ __device__ __forceinline__ double policy_epsilon(const mt_policy &pol, uint64_t c) {
+  if (pol.mode != MT_POLICY_EGREEDY) return 0.0;
+  if (!pol.annealed) return pol.epsilon;
+  const double g = (double)(c * (uint64_t)pol.rows_per_call);
+  return g <= pol.annealing_steps ? pol.epsilon - (g * pol.epsilon / pol.annealing_steps) : 0.0;
+}
+// The explored index of a head of size n, given u < eps (e_greedy_choose's randint): u / eps is
+// uniform on [0, 1); clamped, so the index is in [0, n) whatever eps is.
+__host__ __device__ __forceinline__ int explore_index(int n, double u, double eps) {
+  const double x = floor((u / eps) * (double)n);
+  return !(x >= 0.0) ? 0 : (x > (double)(n - 1) ? n - 1 : (int)x);
+}
+// First maximum in index order, as np.argmax: a NaN counts as the maximum, the first NaN wins.
+__host__ __device__ __forceinline__ bool argmax_takes(float best, float x) {
+  return best == best && (x > best || x != x);
+}
+// The e-greedy / argmax chooser of one head (the multinomial mode is draw_index).
+__host__ __device__ __forceinline__ int choose_index(const float *p, int n, double u, double eps) {
+  if (u < eps) return explore_index(n, u, eps);
+  int best = 0;
+  float bv = p[0];
+  for (int j = 1; j < n; ++j)
+    if (argmax_takes(bv, p[j])) {
+      best = j;
+      bv = p[j];
+    }
+  return best;
+}
+// One row's (a, r) under a policy from its counter value c: the standalone sample kernel and
+// mt_policy_draw_host (the fused heads kernel does the same over lanes, net.hip wave_choose).
+__host__ __device__ __forceinline__ void policy_row(const mt_policy &pol, const float *pa, int A, const float *pr,
+                                                    int R, uint64_t seed, uint64_t global_row, uint64_t c, int *a,
+                                                    int *r) {
+  double ua, ur;
+  row_uniforms(seed, global_row, c, &ua, &ur);
+  if (pol.mode == MT_POLICY_MULTINOMIAL) {
+    *a = draw_index(pa, A, ua);
+    *r = draw_index(pr, R, ur);
+  } else {
+    const double eps = policy_epsilon(pol, c);
+    *a = choose_index(pa, A, ua, eps);
+    *r = choose_index(pr, R, ur, eps);
+  }
+}
+
+__device__ __forceinline__ void sample_row(const mt_policy &pol, const float *pa, int A, const float *pr, int R,
+                                           uint64_t seed, int b, int row0, uint64_t *counters, int *a, int *r) {
   const uint64_t c = counters[b];
   counters[b] = c + 1;
-  double ua, ur;
-  row_uniforms(seed, b + row0, c, &ua, &ur);
-  *a = draw_index(pa, A, ua);
-  *r = draw_index(pr, R, ur);
+  policy_row(pol, pa, A, pr, R, seed, (uint64_t)(b + row0), c, a, r);
 }
+
+// MT_OK, or MT_ERR_ARG with a message, for a policy description (NULL = multinomial: accepted); misc.hip
+int policy_check(const mt_policy *pol, const char *who);
 
 // Rollout-path sampling fused into the heads kernel (mt_rollout_step): indices to device
 // buffers and, when pair != null, to a host-mapped [2][B] pair.
@@ -160,6 +208,8 @@ struct SampleArgs {
   const uint32_t *seq_base = nullptr;
   uint32_t *advance = nullptr;
   uint32_t advance_by = 0;
+  // exploration policy of the draw (mt_policy, by value: a captured graph holds it); zero = multinomial
+  mt_policy policy = {};
 };
 
 }  // namespace mt

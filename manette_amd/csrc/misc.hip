@@ -282,14 +282,15 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
 // ---------------------------------------------------------------------------------------------
 // A3 perf mode: counter-based uniforms, inverse CDF over (p - epsneg(float32)).
 // ---------------------------------------------------------------------------------------------
-__global__ void sample_kernel(const float *__restrict__ pi, const float *__restrict__ rep, int B,
+// (pol: the exploration policy, include/manette_hip.h mt_policy; zero-filled = the multinomial draw)
+__global__ void sample_kernel(mt_policy pol, const float *__restrict__ pi, const float *__restrict__ rep, int B,
                               int A, int R, uint64_t seed, int row0, uint64_t *__restrict__ counters,
                               int32_t *__restrict__ a_idx, int32_t *__restrict__ r_idx,
                               int32_t *__restrict__ pair) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   int a, r;
-  sample_row(pi + (size_t)b * A, A, rep + (size_t)b * R, R, seed, b, row0, counters, &a, &r);
+  sample_row(pol, pi + (size_t)b * A, A, rep + (size_t)b * R, R, seed, b, row0, counters, &a, &r);
   a_idx[b] = a;
   r_idx[b] = r;
   if (pair) {
@@ -463,11 +464,46 @@ extern "C" int mt_host_device_pointer(void *host, void **dev) {
 extern "C" int mt_sample(const float *pi, const float *rep, int batch, int num_actions,
                          int num_reps, uint64_t seed, int row0, uint64_t *counters, int32_t *a_idx,
                          int32_t *r_idx, int32_t *pair, mt_stream_t stream) {
+  return mt_sample_policy(nullptr, pi, rep, batch, num_actions, num_reps, seed, row0, counters, a_idx, r_idx, pair,
+                          stream);
+}
+
+int mt::policy_check(const mt_policy *pol, const char *who) {
+  if (!pol) return MT_OK;
+  MT_CHECK_ARG(pol->mode >= MT_POLICY_MULTINOMIAL && pol->mode <= MT_POLICY_ARGMAX, "%s: policy mode %d outside 0..2",
+               who, (int)pol->mode);
+  MT_CHECK_ARG(pol->epsilon >= 0.0 && pol->epsilon <= 1.0, "%s: policy epsilon %g outside [0, 1]", who, pol->epsilon);
+  MT_CHECK_ARG(!pol->annealed || pol->annealing_steps > 0.0, "%s: an annealed policy needs annealing_steps > 0 (got %g)",
+               who, pol->annealing_steps);
+  // (a zero-filled policy is the multinomial draw: its rows_per_call of 0 is not read)
+  MT_CHECK_ARG(pol->mode == MT_POLICY_MULTINOMIAL || pol->rows_per_call >= 1, "%s: policy rows_per_call %lld < 1", who,
+               (long long)pol->rows_per_call);
+  return MT_OK;
+}
+
+extern "C" int mt_sample_policy(const mt_policy *policy, const float *pi, const float *rep, int batch,
+                                int num_actions, int num_reps, uint64_t seed, int row0, uint64_t *counters,
+                                int32_t *a_idx, int32_t *r_idx, int32_t *pair, mt_stream_t stream) {
   MT_CHECK_ARG(pi && rep && counters && a_idx && r_idx, "null argument");
   MT_CHECK_ARG(batch >= 1 && num_actions >= 1 && num_reps >= 1 && row0 >= 0, "bad sizes");
-  hipLaunchKernelGGL(sample_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, (hipStream_t)stream, pi,
-                     rep, batch, num_actions, num_reps, seed, row0, counters, a_idx, r_idx, pair);
+  if (int rc = policy_check(policy, "mt_sample_policy")) return rc;
+  hipLaunchKernelGGL(sample_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, (hipStream_t)stream,
+                     policy ? *policy : mt_policy{}, pi, rep, batch, num_actions, num_reps, seed, row0, counters,
+                     a_idx, r_idx, pair);
   MT_LAUNCHED();
+  return MT_OK;
+}
+
+extern "C" int mt_policy_draw_host(const mt_policy *policy, uint64_t seed, uint64_t global_row, uint64_t counter,
+                                   const float *pi, int num_actions, const float *rep, int num_reps, int32_t *a,
+                                   int32_t *r) {
+  MT_CHECK_ARG(pi && rep && a && r, "null argument");
+  MT_CHECK_ARG(num_actions >= 1 && num_reps >= 1, "bad sizes");
+  if (int rc = policy_check(policy, "mt_policy_draw_host")) return rc;
+  int ai, ri;
+  policy_row(policy ? *policy : mt_policy{}, pi, num_actions, rep, num_reps, seed, global_row, counter, &ai, &ri);
+  *a = ai;
+  *r = ri;
   return MT_OK;
 }
 

@@ -474,6 +474,21 @@ __device__ __forceinline__ int wave_draw(float p, int n, double u) {
   }
   return res;
 }
+// choose_index (common.h) over probabilities held in lanes [0, n): the e-greedy / argmax chooser. The
+// first-maximum search walks n readlanes, as wave_draw does: values and the running best are
+// wave-uniform, so the walk is scalar compares and selects.
+__device__ __forceinline__ int wave_choose(float p, int n, double u, double eps) {
+  float bv = lane_f(p, 0);
+  int best = 0;
+  for (int j = 1; j < n; ++j) {
+    const float pj = lane_f(p, j);
+    if (argmax_takes(bv, pj)) {
+      best = j;
+      bv = pj;
+    }
+  }
+  return u < eps ? explore_index(n, u, eps) : best;
+}
 
 // One workgroup per row b (NT / 64 waves: 4 for F <= 256, 8 for F <= 512):
 //  1. h = act(sum_z slabs[z][b] + b_fc) — the split-K dense layer finished here
@@ -494,7 +509,7 @@ __device__ __forceinline__ int wave_draw(float p, int n, double u) {
 constexpr int kHeadQ = 8;  // region quads per thread held in registers from the kernel start
 __device__ uint64_t g_zero_u64 = 0;  // read in place of an absent draw counter / sequence base
 
-template <int FT, int SB, int NT>
+template <int FT, int SB, int NT, bool POL>
 __device__ __forceinline__ void heads_row(int b, const float *__restrict__ slabs, int S, int B,
                                           const float *__restrict__ fc_b, int act, float alpha, const HeadParams &hp,
                                           float temp, float *__restrict__ H, float *__restrict__ v,
@@ -537,6 +552,9 @@ __device__ __forceinline__ void heads_row(int b, const float *__restrict__ slabs
   }
   double ua = 0.0, ur = 0.0;
   if (w == 0) row_uniforms(smp.seed, b + smp.row0, cnt, &ua, &ur);
+  // POL (e-greedy / argmax draw): the call's epsilon from the same counter, in the same shadow
+  double eps = 0.0;
+  if (POL && w == 0) eps = policy_epsilon(smp.policy, cnt);
   // slab sum in slab order + bias + activation
 #pragma unroll
   for (int fi = 0; fi < FT; ++fi) {
@@ -635,7 +653,8 @@ __device__ __forceinline__ void heads_row(int b, const float *__restrict__ slabs
   if (lane < hp.A) pi[(size_t)b * hp.A + lane] = pa;
   if (lane < hp.R) rep[(size_t)b * hp.R + lane] = pr;
   if (smp.counters) {
-    const int a = wave_draw(pa, hp.A, ua), r = wave_draw(pr, hp.R, ur);
+    const int a = POL ? wave_choose(pa, hp.A, ua, eps) : wave_draw(pa, hp.A, ua);
+    const int r = POL ? wave_choose(pr, hp.R, ur, eps) : wave_draw(pr, hp.R, ur);
     if (lane == 0) {
       const uint32_t seq = seq_base + smp.seq;  // (graph replay: device base)
       if (smp.packed) {  // tagged pair, one 8-byte store, no fence (SampleArgs::packed)
@@ -657,7 +676,10 @@ __device__ __forceinline__ void heads_row(int b, const float *__restrict__ slabs
   }
 }
 
-template <int FT, int SB, int NT>
+// POL: the draw's exploration policy is e-greedy or argmax (SampleArgs::policy). A template parameter,
+// not a run-time branch: the multinomial kernel (POL = false) is instruction for instruction the one
+// it was before the policy modes, on the single wave that ends every macro-step's chain.
+template <int FT, int SB, int NT, bool POL>
 __global__ __launch_bounds__(NT) void heads_fwd_kernel(const float *__restrict__ slabs, int S, int B,
                                                         const float *__restrict__ fc_b, int act,
                                                         float alpha, HeadParams hp, float temp,
@@ -666,7 +688,7 @@ __global__ __launch_bounds__(NT) void heads_fwd_kernel(const float *__restrict__
                                                         float *__restrict__ rep, SampleArgs smp) {
   extern __shared__ __attribute__((aligned(16))) float head_region[];
   MT_PROBE_AT(2, blockIdx.x, 0);
-  heads_row<FT, SB, NT>(blockIdx.x, slabs, S, B, fc_b, act, alpha, hp, temp, H, v, pi, rep, smp, head_region);
+  heads_row<FT, SB, NT, POL>(blockIdx.x, slabs, S, B, fc_b, act, alpha, hp, temp, H, v, pi, rep, smp, head_region);
   MT_PROBE_AT(2, blockIdx.x, 3);
 }
 
@@ -686,16 +708,23 @@ static int launch_heads(int rows, hipStream_t s, const float *slabs, int S, int 
     set_error("heads: head region of %zu bytes exceeds the LDS", lds);
     return MT_ERR_ARG;
   }
-#define MT_HEADS(FT_, SB_, NT_)                                                                              \
+#define MT_HEADS_(FT_, SB_, NT_, POL_)                                                                       \
   do {                                                                                                       \
     static bool attr_set = false;                                                                            \
     if (!attr_set && lds > 64 * 1024) {                                                                      \
-      MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&heads_fwd_kernel<FT_, SB_, NT_>),           \
+      MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&heads_fwd_kernel<FT_, SB_, NT_, POL_>),     \
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));  \
       attr_set = true;                                                                                       \
     }                                                                                                        \
-    hipLaunchKernelGGL((heads_fwd_kernel<FT_, SB_, NT_>), dim3(rows), dim3(NT_), lds, s, slabs, S, B, fc_b,    \
-                       act, alpha, hp, temp, H, v, pi, rep, smp);                                            \
+    hipLaunchKernelGGL((heads_fwd_kernel<FT_, SB_, NT_, POL_>), dim3(rows), dim3(NT_), lds, s, slabs, S, B,    \
+                       fc_b, act, alpha, hp, temp, H, v, pi, rep, smp);                                      \
+  } while (0)
+#define MT_HEADS(FT_, SB_, NT_)                                                 \
+  do {                                                                          \
+    if (smp.counters && smp.policy.mode != MT_POLICY_MULTINOMIAL)               \
+      MT_HEADS_(FT_, SB_, NT_, true);                                           \
+    else                                                                        \
+      MT_HEADS_(FT_, SB_, NT_, false);                                          \
   } while (0)
   if (hp.F <= 256) {
     if (S <= 1) MT_HEADS(1, 1, 256);
@@ -707,6 +736,7 @@ static int launch_heads(int rows, hipStream_t s, const float *slabs, int S, int 
     else MT_HEADS(1, 16, 512);
   }
 #undef MT_HEADS
+#undef MT_HEADS_
   MT_LAUNCHED();
   return MT_OK;
 }

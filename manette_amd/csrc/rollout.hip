@@ -20,6 +20,8 @@ struct mt_rollout {
   mh_book *book;
   mt_rollout_buffers b;
   uint64_t seed;
+  mt_policy policy = {};  // the fused draw's exploration policy (mt_rollout_set_policy; zero = multinomial)
+  bool stepped = false;   // a macro-step has run: the policy is fixed (the replayed graph bakes it in)
   std::vector<hipEvent_t> ev;  // [T] pair of step t ready (recorded once per rollout: chains are armed
                                // up to T steps ahead)
   bool zero_copy, in_place, pooled, resized, pipelined;
@@ -423,6 +425,7 @@ int enqueue_forward(mt_rollout *ro, const float *params, int t, hipStream_t s, b
   }
   smp.packed = ro->packed_dev;
   smp.row0 = b.env_offset;
+  smp.policy = ro->policy;
   // with a train workspace: activations into its rows t*E.., per-step pi / rep (mt_forward_rows)
   const TrainRows tr{(float *)b.train_ws, b.train_ws_bytes, T * E, t * E};
   const size_t po = b.train_ws ? (size_t)t * E : 0;
@@ -644,6 +647,7 @@ extern "C" int mt_rollout_step(mt_rollout *ro, const float *params, int t, int64
                "must not share a hardware queue with another stream's): got %p after %p", (void *)s,
                (void *)ro->stream0);
   const int E = ro->E, T = ro->T;
+  ro->stepped = true;
   const double t0 = now_us();
   int32_t *a_h = b.idx_host + (size_t)t * E, *r_h = b.idx_host + (size_t)T * E + (size_t)t * E;
   // 1. forward + draw of step t, unless a previous call already enqueued it
@@ -783,6 +787,15 @@ extern "C" int mt_rollout_step(mt_rollout *ro, const float *params, int t, int64
 extern "C" int mt_rollout_run(mt_rollout *ro, const float *params, int64_t *global_step, mt_stream_t stream) {
   MT_CHECK_ARG(ro && params && global_step, "null argument");
   for (int t = 0; t < ro->T; ++t) MT_TRY_(mt_rollout_step(ro, params, t, global_step, stream));
+  return MT_OK;
+}
+
+extern "C" int mt_rollout_set_policy(mt_rollout *ro, const mt_policy *policy) {
+  MT_CHECK_ARG(ro, "null argument");
+  MT_CHECK_ARG(!ro->stepped, "mt_rollout_set_policy: the rollout has stepped (its replayed graph holds the policy "
+               "by value); set the policy before the first mt_rollout_step");
+  if (int rc = policy_check(policy, "mt_rollout_set_policy")) return rc;
+  ro->policy = policy ? *policy : mt_policy{};
   return MT_OK;
 }
 

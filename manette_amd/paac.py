@@ -12,7 +12,8 @@ Paths (args.runner):
   'python'  reference-contract Python emulators (Runners / EmulatorRunner processes); finished
             84x84xC observations go H2D.
 Sampling (args.sampling): 'host' = the reference's numpy multinomial stream (parity mode),
-'device' = mt_sample (perf mode, same distribution).
+'device' = mt_sample (perf mode, same distribution), or with --egreedy / a test policy the e-greedy /
+argmax draw of mt_policy (mt_sample_policy, mt_rollout_set_policy), epsilon annealed on the device.
 Data parallel: one process per GPU; env ids are offset by rank (rank r owns global envs
 [r*ec, (r+1)*ec), the runners.py:17-18 split over ranks), each rank rolls out its own shard and
 the flat gradient is summed by ONE all-reduce per update (RCCL behind the C ABI, mt_allreduce,
@@ -86,9 +87,18 @@ class PAACLearner(ActorLearner):
         # code the N-GPU run depends on runs, and is oracle-checked, on one GPU (tests/test_e2e_gpu.py)
         self.dp = self.world > 1 or bool(getattr(args, 'dp_force', False)) or os.environ.get('MT_DP_FORCE') == '1'
         self.grad_scale = 1.0 / self.world  # folded into clip + RMSProp: the all-reduced sum -> the mean
-        if self.sampling == 'device' and getattr(args, 'egreedy', False):
-            # the device draw is the multinomial of exploration_policy.py:108-116 only
-            raise ValueError('--egreedy needs --sampling host (the device sampler draws multinomially)')
+        # the device draw's chooser (exploration_policy.py:78-87; include/manette_hip.h mt_policy): None =
+        # the multinomial draw. Epsilon anneals on the device from each row's draw counter:
+        # rows_per_call = what the reference's global_step grows by per choose call, every env of the job.
+        self.policy = None
+        if self.sampling == 'device' and (getattr(explo_policy, 'test', False) or getattr(args, 'egreedy', False)):
+            from . import _lib
+            if getattr(explo_policy, 'test', False):
+                self.policy = _lib.mt_policy(_lib.MT_POLICY['argmax'], 0, 0.0, 0.0, 1)
+            else:
+                self.policy = _lib.mt_policy(_lib.MT_POLICY['egreedy'], int(bool(getattr(args, 'annealed', False))),
+                                             float(args.epsilon), float(getattr(args, 'annealed_steps', 80000000)),
+                                             self.world * self.emulator_counts)
         self.dev = self.network.device
         E, T, C = self.emulator_counts, self.max_local_steps, self.C
         dev = self.dev
@@ -287,6 +297,8 @@ class PAACLearner(ActorLearner):
                                                 self.book.handle, C.byref(self._bufs),
                                                 C.c_uint64(self.sample_seed), C.byref(h)), 'mt_rollout_create')
         self.native_step = h
+        if self.policy is not None:  # before the first step: the replayed rollout graph holds it by value
+            _lib.check(_lib.hip().mt_rollout_set_policy(h, C.byref(self.policy)), 'mt_rollout_set_policy')
         self._over_dev = devnet.host_device_pointer(r.over) if self.lstm_bool else None
         self.boot_in_rollout = self.pipeline  # the last step's chain runs the bootstrap forward
         # the rollout's stacking forward (pipelined, resized staging; NIPS, gray NATURE) also carries
@@ -363,7 +375,8 @@ class PAACLearner(ActorLearner):
         if end is not None:
             end.record()
         if self.sampling == 'device':
-            devnet.sample(pi, rep, self.sample_seed, self.counters, self.a_idx[t], self.r_idx[t], row0=self.env_offset)
+            devnet.sample(pi, rep, self.sample_seed, self.counters, self.a_idx[t], self.r_idx[t], row0=self.env_offset,
+                          policy=self.policy)
             self.a_h[t].copy_(self.a_idx[t], non_blocking=True)
             self.r_h[t].copy_(self.r_idx[t], non_blocking=True)
             self.event.record()

@@ -10,7 +10,9 @@ offset by rank, args.json records both counts, and gradients are all-reduced by 
 C ABI (--comm rccl; torch.distributed runs on gloo as the control channel only).
 Sampling: --sampling host (the default) draws with the reference's numpy multinomial stream
 (exploration_policy.py:108-116, bit-exact parity with the reference); the benchmarked native
-macro-step (bench.py) is --sampling device.
+macro-step (bench.py) is --sampling device, which also takes --egreedy, --epsilon, --annealed and
+--annealed_steps (the e-greedy draw and its annealing run in the heads kernel: mt_policy,
+include/manette_hip.h).
 """
 import argparse
 import copy
@@ -165,7 +167,7 @@ def get_arg_parser():
     parser.add_argument('--no_pipeline', action='store_false', help='native device-sampling step: do not enqueue '
                         'step t+1\'s preprocess + forward behind a device wait on a host step word '
                         '(MT_ROLLOUT_PIPELINED, on by default)', dest='pipeline')
-    parser.add_argument('--sampling', default='host', choices=['host', 'device'], help='host (default): numpy multinomial, the reference\'s stream (parity mode); device: mt_sample fused into the heads kernel, the benchmarked native macro-step', dest='sampling')
+    parser.add_argument('--sampling', default='host', choices=['host', 'device'], help='host (default): numpy multinomial, the reference\'s stream (parity mode); device: the draw fused into the heads kernel (multinomial, or e-greedy with --egreedy / --epsilon / --annealed / --annealed_steps), the benchmarked native macro-step', dest='sampling')
     parser.add_argument('--ec_scope', default='rank', choices=['rank', 'global'], help='data parallel: -ec emulators per rank (rank, the reference\'s meaning for one process) or for the whole job, split evenly over WORLD_SIZE ranks (global)', dest='ec_scope')
     parser.add_argument('--seed', default=0, type=int, help='parameter init / device sampling seed', dest='seed')
     parser.add_argument('--comm', default='rccl', choices=['rccl', 'torch'], help='data-parallel gradient all-reduce: '
