@@ -123,8 +123,16 @@ int mt_net_workspace_region(const mt_net *net, int layout, int a, int b, int kin
  * activation, before dropout); kind 2 stays the features the heads read (H4).
  * mt_forward, mt_forward_infer and mt_forward_rows run the stage (mt_forward_rows: state and counters
  * of the batch-row `ws`; H3, mask and H4 land in the train rows); mt_loss_backward runs its backward
- * under the mask the workspace holds. mt_returns_loss_backward[_boot], mt_forward_trunk_stacking and
- * mt_rollout_create return MT_ERR_UNSUPPORTED, as does mt_net_backward_bucket_launches. */
+ * under the mask the workspace holds. The update in one call is mt_dropout_returns_loss_backward
+ * (redraw + n-step scan + loss + backward). mt_returns_loss_backward[_boot], mt_forward_trunk_stacking
+ * and mt_net_backward_bucket_launches return MT_ERR_UNSUPPORTED.
+ * The native macro-step is opt-in: mt_rollout_create returns MT_ERR_UNSUPPORTED for this arch unless
+ * flags carry MT_ROLLOUT_DROPOUT. With the bit, every staging / pipelining mode of a NIPS net is
+ * accepted except MT_ROLLOUT_BOOT_SLABS (MT_ERR_ARG: V(s_T) needs the stage, so the bootstrap chain runs
+ * stage + heads). Each step forward t = 0..T-1 and then the bootstrap draw from the dropout state of the
+ * rollout's `ws`, one counter value per row each — from the replayed rollout graph too: the stream is
+ * device state, never a kernel argument — and steps t < T leave H3, mask, D and H4 in train rows t*E..,
+ * as mt_forward_rows does. */
 
 /* out[256] = the mask of (seed, global_row, counter) at keep_prob, 0 / 1 (host restatement of the
  * formula above; the kernels are pinned against it). */
@@ -136,6 +144,22 @@ int mt_dropout_mask_host(uint64_t seed, uint64_t global_row, uint64_t counter, f
  * activation is written. BAYESIAN only (MT_ERR_UNSUPPORTED otherwise). */
 int mt_dropout_redraw(const mt_net *net, const float *params, int batch, void *ws, size_t ws_bytes, float *v,
                       float *pi, float *rep, mt_stream_t stream);
+
+/* The BAYESIAN update's backward in one call (batch = T*E rows t*E+e): mt_returns + mt_dropout_redraw +
+ * mt_loss_backward (+ mt_grad_sumsq with norm_partials), bit for bit. Launches: the redraw stage over
+ * the H3 rows a rollout left in `ws` (fresh masks, one counter value per row), the heads kernel (v_out
+ * [T*E], pi_out, rep_out = v', pi', rep'), then the loss kernel, whose block of row (t, e) runs env e's
+ * n-step scan itself (mt_returns' arithmetic) and takes adv = R - values[t][e] — the ROLLOUT's value —
+ * while the critic term and loss_terms use v'[t][e]; then the backward's grouped launches. rewards /
+ * masks [T][E] may be pinned host memory read in place. y, adv [T][E] are written. norm_partials (may be
+ * NULL): as mt_returns_loss_backward's. No allocation, no synchronisation: capturable. BAYESIAN only
+ * (MT_ERR_UNSUPPORTED otherwise). */
+int mt_dropout_returns_loss_backward(const mt_net *net, const float *params, const uint8_t *obs, int T, int E,
+                                     void *ws, size_t ws_bytes, const float *values, const int32_t *a_idx,
+                                     const int32_t *r_idx, const float *rewards, const float *masks,
+                                     const float *v_boot, double gamma, float *v_out, float *pi_out, float *rep_out,
+                                     float *y, float *adv, float entropy_beta, float *grad, float *loss_terms,
+                                     float *norm_partials, mt_stream_t stream);
 
 /* ---- forward (A5-A7) ----------------------------------------------------------------------
  * Replaces session.run([output_layer_v, output_layer_pi, output_layer_rep], {input_ph: s})
@@ -444,6 +468,9 @@ int mt_memory_push(uint8_t *memory, uint8_t *whole_t, const uint8_t *fresh, cons
  * finishes V(s_T) itself (mt_returns_loss_backward_boot, which writes v_boot): one heads kernel and
  * one kernel boundary fewer between the last emulator step and the backward. */
 #define MT_ROLLOUT_BOOT_SLABS 32
+/* flags & MT_ROLLOUT_DROPOUT: accept a BAYESIAN net (see "BAYESIAN arch" above; without the bit it is
+ * refused with MT_ERR_UNSUPPORTED). MT_ERR_ARG on any other arch, and together with BOOT_SLABS. */
+#define MT_ROLLOUT_DROPOUT 64
 typedef struct mt_rollout mt_rollout;
 typedef struct mt_rollout_buffers {
   /* device */

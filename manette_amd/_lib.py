@@ -38,6 +38,7 @@ MT_ROLLOUT_POOLED = 4
 MT_ROLLOUT_PIPELINED = 8
 MT_ROLLOUT_RESIZED = 16
 MT_ROLLOUT_BOOT_SLABS = 32
+MT_ROLLOUT_DROPOUT = 64
 MH_RUNNER_RESIZED = 4
 MH_RUNNER_FIXED_SLOTS = 1
 MH_RUNNER_POOLED = 2
@@ -95,6 +96,8 @@ _HIP_SIGS = {
     'mt_returns': (_I, [_P, _P, _P, _P, C.c_double, _I, _I, _P, _P, _P]),
     'mt_loss_backward': (_I, [_P, _P, _P, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     'mt_dropout_redraw': (_I, [_P, _P, _I, _P, _SZ, _P, _P, _P, _P]),
+    'mt_dropout_returns_loss_backward': (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, C.c_double, _P, _P,
+                                              _P, _P, _P, _F, _P, _P, _P, _P]),
     'mt_dropout_mask_host': (_I, [C.c_uint64, C.c_uint64, C.c_uint64, _F, _P]),
     'mt_returns_loss_backward': (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, _P,
                                       _F, _P, _P, _P, _P]),

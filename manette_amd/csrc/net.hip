@@ -792,6 +792,9 @@ struct ReturnsSrc {
   const float *boot_slabs = nullptr, *fc_b = nullptr;
   int boot_S = 0;
   float *vt_out = nullptr;
+  // BAYESIAN (mt_dropout_returns_loss_backward, the kernel's RV variant): the rollout's values [T][E].
+  // adv = R - v_roll[b], while the critic term and loss_terms keep the kernel's `v` (the redrawn v')
+  const float *v_roll = nullptr;
 };
 
 // V(s_T)[e] of the bootstrap (ReturnsSrc::boot_slabs): the dense layer's split-K slabs summed in
@@ -903,6 +906,9 @@ __device__ __forceinline__ void row_return(const ReturnsSrc &rs, float vb, int b
   __syncthreads();
 }
 
+// RV (compile-time, BAYESIAN's fused update): the advantage's value is rs.v_roll[b], loaded with the
+// row's other head inputs ahead of the scan; RV = false is the kernel of every other arch, unchanged.
+template <bool RV>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(
     HeadParams hp, const float *__restrict__ H, const float *__restrict__ pi,
     const float *__restrict__ rep, const float *__restrict__ v, const int32_t *__restrict__ a_idx,
@@ -924,11 +930,13 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(
   // ahead of the bootstrap slab loads).
   const int lane = threadIdx.x;
   float pa = 0.f, pr = 0.f, vb = 0.f, adv_in = 0.f, y_in = 0.f;
+  [[maybe_unused]] float vroll = 0.f;
   int ai = 0, ri = 0;
   if (threadIdx.x < 64) {
     pa = lane < A ? pi[(size_t)b * A + lane] : 0.f;
     pr = lane < R ? rep[(size_t)b * R + lane] : 0.f;
     vb = v[b];
+    if constexpr (RV) vroll = rs.v_roll[b];
     ai = a_idx[b];
     ri = r_idx[b];
     if (!rs.r) {
@@ -977,7 +985,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(
       vt = rs.VT[b % rs.E];
     }
     MT_PROBE_AT(4, b, 1);
-    row_return(rs, vb, b, vt, rk, mk, ya, buf);
+    row_return(rs, RV ? vroll : vb, b, vt, rk, mk, ya, buf);
   }
   MT_PROBE_AT(4, b, 2);
   if (!staged) stage();  // (visible to every thread after the barrier below)
@@ -1528,13 +1536,22 @@ static int loss_bwd_launch(const mt_net *n, const float *P, int B, float *ws, co
   }
   static bool attr_set = false;
   if (!attr_set && lds > 64 * 1024) {
-    MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&loss_bwd_kernel),
+    MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&loss_bwd_kernel<false>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));
+    MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&loss_bwd_kernel<true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));
     attr_set = true;
   }
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(B), dim3(256), lds, s, hp, ws + L.H, pi, rep, v, a_idx, r_idx, y, adv,
-                     beta, scale, n->cfg.softmax_temp, n->cfg.activation, n->cfg.alpha_leaky, ws + L.dz, ws + L.dH,
-                     loss_terms, rs);
+  if (rs.v_roll) {  // (only with the scan: mt_dropout_returns_loss_backward)
+    MT_CHECK_ARG(rs.r && !rs.boot_slabs, "rollout values need the in-kernel scan with a finished v_boot");
+    hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(B), dim3(256), lds, s, hp, ws + L.H, pi, rep, v, a_idx, r_idx, y,
+                       adv, beta, scale, n->cfg.softmax_temp, n->cfg.activation, n->cfg.alpha_leaky, ws + L.dz,
+                       ws + L.dH, loss_terms, rs);
+  } else {
+    hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(B), dim3(256), lds, s, hp, ws + L.H, pi, rep, v, a_idx, r_idx, y,
+                       adv, beta, scale, n->cfg.softmax_temp, n->cfg.activation, n->cfg.alpha_leaky, ws + L.dz,
+                       ws + L.dH, loss_terms, rs);
+  }
   MT_LAUNCHED();
   return MT_OK;
 }
@@ -1623,6 +1640,22 @@ static int backward_impl(const mt_net *n, const float *P, const uint8_t *obs, in
   if constexpr (nips_fused_bwd<Ar>())
     if (B <= kNipsFusedBwdMaxRows) return nips_conv_backward<Ar>(n, P, obs, B, ws, L, grad, s, no);
   return trunk_backward<Ar, K>(n, P, obs, B, ws, L, grad, s, SlabJob{}, no);
+}
+
+// BAYESIAN: the train step's fresh mask over the H3 rows of `w` (mt_dropout_redraw): the forward stage's
+// kernel with the slab sum replaced by a load of the stored H3: fresh masks -> D -> Z4 -> heads; H3 and
+// the conv activations are only read
+template <class Ar>
+static int dropout_redraw_impl(const mt_net *net, const float *params, int batch, float *w, const WsLayout &L, float *v,
+                               float *pi, float *rep, hipStream_t s) {
+  const ActRows A{w, L, L.H};
+  DropoutFcArgs d = dropout_args<Ar>(net, params, batch, A, 0);
+  d.state = reinterpret_cast<uint64_t *>(w + L.dstate);
+  d.Z4 = w + L.z4;
+  MT_TRY(launch_dropout_fc(d, s));
+  HeadParams hp = head_params(net, params);
+  return launch_heads(batch, s, d.Z4, 1, batch, d.W4 + (size_t)Ar::DROP_F * Ar::F, net->cfg.activation,
+                      net->cfg.alpha_leaky, hp, net->cfg.softmax_temp, w + L.H, v, pi, rep, SampleArgs{});
 }
 
 }  // namespace mt
@@ -2039,18 +2072,52 @@ extern "C" int mt_dropout_redraw(const mt_net *net, const float *params, int bat
         set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
         return MT_ERR_WORKSPACE;
       }
-      // the forward stage's kernel with the slab sum replaced by a load of the stored H3: fresh masks
-      // -> D -> Z4 -> heads; H3 and the conv activations are only read
-      float *w = (float *)ws;
-      const ActRows A{w, L, L.H};
-      DropoutFcArgs d = dropout_args<Ar>(net, params, batch, A, 0);
-      d.state = reinterpret_cast<uint64_t *>(w + L.dstate);
-      d.Z4 = w + L.z4;
-      MT_TRY(launch_dropout_fc(d, (hipStream_t)stream));
-      HeadParams hp = head_params(net, params);
-      return launch_heads(batch, (hipStream_t)stream, d.Z4, 1, batch, d.W4 + (size_t)Ar::DROP_F * Ar::F,
-                          net->cfg.activation, net->cfg.alpha_leaky, hp, net->cfg.softmax_temp, w + L.H, v, pi, rep,
-                          SampleArgs{});
+      return dropout_redraw_impl<Ar>(net, params, batch, (float *)ws, L, v, pi, rep, (hipStream_t)stream);
+    }
+  });
+  return MT_OK;
+}
+
+extern "C" int mt_dropout_returns_loss_backward(const mt_net *net, const float *params, const uint8_t *obs, int T,
+                                                int E, void *ws, size_t ws_bytes, const float *values,
+                                                const int32_t *a_idx, const int32_t *r_idx, const float *rewards,
+                                                const float *masks, const float *v_boot, double gamma, float *v_out,
+                                                float *pi_out, float *rep_out, float *y, float *adv,
+                                                float entropy_beta, float *grad, float *loss_terms,
+                                                float *norm_partials, mt_stream_t stream) {
+  MT_CHECK_ARG(net && params && obs && ws && values && a_idx && r_idx && rewards && masks && v_boot && v_out &&
+                   pi_out && rep_out && y && adv && grad,
+               "null argument");
+  MT_CHECK_ARG(T >= 1 && E >= 1 && T <= kMaxScan, "T=%d (<= %d) and E=%d must be >= 1", T, kMaxScan, E);
+  const int batch = T * E;
+  MT_ARCH_SWITCH(net, {
+    if constexpr (Ar::DROP_F == 0) {
+      set_error("mt_dropout_returns_loss_backward: the BAYESIAN arch only");
+      return MT_ERR_UNSUPPORTED;
+    } else {
+      const WsLayout L = ws_layout<Ar>(net, batch);
+      if (ws_bytes < L.total * sizeof(float)) {
+        set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
+        return MT_ERR_WORKSPACE;
+      }
+      // the train step's fresh mask (v', pi', rep'; mask, D and H4 for the backward), then the loss kernel
+      // scans with the ROLLOUT's values for the advantage and takes the critic from v'
+      MT_TRY(dropout_redraw_impl<Ar>(net, params, batch, (float *)ws, L, v_out, pi_out, rep_out, (hipStream_t)stream));
+      ReturnsSrc rs;
+      rs.r = rewards;
+      rs.mask = masks;
+      rs.VT = v_boot;
+      rs.gamma = gamma;
+      rs.T = T;
+      rs.E = E;
+      rs.y_out = y;
+      rs.adv_out = adv;
+      rs.v_roll = values;
+      NormOut no;
+      no.partials = norm_partials;
+      no.n = net->nparams;
+      return backward_impl<Ar>(net, params, obs, batch, (float *)ws, pi_out, rep_out, v_out, a_idx, r_idx, y, adv,
+                               entropy_beta, grad, loss_terms, (hipStream_t)stream, rs, no);
     }
   });
   return MT_OK;

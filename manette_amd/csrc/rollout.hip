@@ -104,11 +104,19 @@ extern "C" int mt_rollout_create(const mt_net *net, int E, int T, void *runner, 
   {
     mt_net_config c0;
     MT_CHECK_ARG(mt_net_get_config(net, &c0) == MT_OK, "bad net");
-    if (c0.arch == MT_ARCH_BAYESIAN) {  // (refused before any buffer is touched)
+    // BAYESIAN is opt-in (MT_ROLLOUT_DROPOUT); without the bit: refused before any buffer is touched
+    if (c0.arch == MT_ARCH_BAYESIAN && !(buffers->flags & MT_ROLLOUT_DROPOUT)) {
       set_error("mt_rollout_create: the native macro-step is not built for the BAYESIAN arch (step with "
                 "mt_forward_rows + mt_sample, update with mt_returns, mt_dropout_redraw and mt_loss_backward)");
       return MT_ERR_UNSUPPORTED;
     }
+    MT_CHECK_ARG(c0.arch == MT_ARCH_BAYESIAN || !(buffers->flags & MT_ROLLOUT_DROPOUT),
+                 "MT_ROLLOUT_DROPOUT is for the BAYESIAN arch");
+    // V(s_T) needs the dropout + fc4 stage between the dense slabs and the critic: the bootstrap chain
+    // runs stage + heads, the loss kernel cannot finish it from the slabs
+    MT_CHECK_ARG(c0.arch != MT_ARCH_BAYESIAN || !(buffers->flags & MT_ROLLOUT_BOOT_SLABS),
+                 "MT_ROLLOUT_BOOT_SLABS is not built for the BAYESIAN arch (its bootstrap runs the dropout + fc4 "
+                 "stage and the heads kernel)");
   }
   const mt_rollout_buffers &b = *buffers;
   const bool ip = (b.flags & MT_ROLLOUT_IN_PLACE) != 0;
@@ -117,7 +125,7 @@ extern "C" int mt_rollout_create(const mt_net *net, int E, int T, void *runner, 
   const bool po = (b.flags & MT_ROLLOUT_POOLED) != 0;
   const bool rz = (b.flags & MT_ROLLOUT_RESIZED) != 0;
   MT_CHECK_ARG((b.flags & ~(MT_ROLLOUT_ZERO_COPY | MT_ROLLOUT_IN_PLACE | MT_ROLLOUT_POOLED | MT_ROLLOUT_PIPELINED |
-                            MT_ROLLOUT_RESIZED | MT_ROLLOUT_BOOT_SLABS)) == 0,
+                            MT_ROLLOUT_RESIZED | MT_ROLLOUT_BOOT_SLABS | MT_ROLLOUT_DROPOUT)) == 0,
                "unknown rollout flags %d", b.flags);
   MT_CHECK_ARG(!(b.flags & MT_ROLLOUT_BOOT_SLABS) || (pl && b.v_boot && !b.nz),
                "MT_ROLLOUT_BOOT_SLABS needs a pipelined, non-LSTM rollout with v_boot");
@@ -180,9 +188,11 @@ extern "C" int mt_rollout_create(const mt_net *net, int E, int T, void *runner, 
   ro->resized = rz;
   ro->pipelined = pl;
   ro->pull = pl && rz;
-  // the stacking chains: NIPS (nips_conv_kernel<STACK>) and gray NATURE (conv1 = DFwdStack): each
-  // env's conv1 waits for its own publication, no pull / preprocess kernel in front of the convs
-  ro->stack_fwd = ro->pull && (cfg.arch == MT_ARCH_NIPS || (cfg.arch == MT_ARCH_NATURE && cfg.depth == 1));
+  // the stacking chains: NIPS and BAYESIAN (its trunk is the NIPS trunk: nips_conv_kernel<STACK>) and
+  // gray NATURE (conv1 = DFwdStack): each env's conv1 waits for its own publication, no pull /
+  // preprocess kernel in front of the convs
+  ro->stack_fwd = ro->pull && (cfg.arch == MT_ARCH_NIPS || cfg.arch == MT_ARCH_BAYESIAN ||
+                               (cfg.arch == MT_ARCH_NATURE && cfg.depth == 1));
   ro->lstm = lstm;
   ro->lstm_stack = ro->pull && lstm;
   ro->frame_stack = ro->pull && !lstm && cfg.arch == MT_ARCH_PWYX;
@@ -539,7 +549,7 @@ int arm_step(mt_rollout *ro, const float *params, int k, int ahead, hipStream_t 
   return MT_OK;
 }
 
-// The replayed rollout graph applies to the stacking chains (NIPS, gray NATURE) with the bootstrap in the last
+// The replayed rollout graph applies to the stacking chains (NIPS, BAYESIAN, gray NATURE) with the bootstrap in the last
 // chain, every chain armed at step 0, after a first eager rollout (step 0's forward then takes
 // slot 0 from slot T), without trunk timing (its events are per launch).
 bool graph_eligible(const mt_rollout *ro) {

@@ -237,6 +237,23 @@ class DeviceNetwork(object):
                                            _ptr(rep), _stream()), 'mt_dropout_redraw')
         return v, pi, rep
 
+    def dropout_returns_loss_backward(self, obs, T, E, values, a_idx, r_idx, rewards, masks, v_boot, gamma, out, y,
+                                      adv, loss_terms=None, ws_key=None, norm_partials=False):
+        """mt_dropout_returns_loss_backward: mt_returns + mt_dropout_redraw + mt_loss_backward in one call
+        over the rows a rollout left in the train workspace. values [T][E]: the rollout's v (the
+        advantage); out = (v', pi', rep') of the fresh mask (the critic, the policy terms). rewards /
+        masks: [T][E] device tensors or device addresses. norm_partials: as returns_loss_backward's."""
+        B = int(T) * int(E)
+        ws = self.workspace(B, ws_key)
+        v, pi, rep = out
+        addr = lambda x: C.c_void_p(x) if isinstance(x, int) else _ptr(x)
+        check(_lib.hip().mt_dropout_returns_loss_backward(
+            self._h, _ptr(self.params), _ptr(obs), int(T), int(E), _ptr(ws), ws.numel(), _ptr(values), _ptr(a_idx),
+            _ptr(r_idx), addr(rewards), addr(masks), _ptr(v_boot), float(gamma), _ptr(v), _ptr(pi), _ptr(rep),
+            _ptr(y), _ptr(adv), self.beta, _ptr(self.grad), _ptr(loss_terms),
+            _ptr(self.partials if norm_partials else None), _stream()), 'mt_dropout_returns_loss_backward')
+        return self.grad
+
     # ---- compute -----------------------------------------------------------------------------
     def forward(self, obs, batch=None, out=None, ws_key=None, infer=False):
         """obs: uint8 cuda tensor [B,84,84,4*depth]. Returns (v, pi, rep) device tensors.

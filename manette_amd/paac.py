@@ -47,8 +47,16 @@ def merge_episode_records(parts):
     return sorted((int(g), float(r), int(n)) for part in parts for (g, r, n) in part)
 
 
+def check_arch_flags(args):
+    """Flags that belong to one arch, checked before anything is allocated (train.py, PAACLearner):
+    --bayes_native switches the BAYESIAN arch to the native macro-step and the captured, fused update."""
+    if getattr(args, 'bayes_native', False) and getattr(args, 'arch', None) != 'BAYESIAN':
+        raise ValueError('--bayes_native is for --arch BAYESIAN (got --arch %s)' % getattr(args, 'arch', None))
+
+
 class PAACLearner(ActorLearner):
     def __init__(self, network_creator, environment_creator, explo_policy, args):
+        check_arch_flags(args)
         self.seed = int(getattr(args, 'seed', 0))
         super(PAACLearner, self).__init__(network_creator, environment_creator, explo_policy, args)
         self.workers = args.emulator_workers
@@ -58,6 +66,9 @@ class PAACLearner(ActorLearner):
         # dropout in every forward, a fresh mask in the train step (networks.py:194-204): Python step(),
         # eager update with mt_dropout_redraw (update()), never the native macro-step or a captured update
         self.bayes_bool = (args.arch == 'BAYESIAN')
+        # ... unless --bayes_native: the native macro-step (MT_ROLLOUT_DROPOUT), the update's backward as
+        # one call (mt_dropout_returns_loss_backward) and the update captured and replayed as for NIPS
+        self.bayes_native = self.bayes_bool and bool(getattr(args, 'bayes_native', False))
         self.tab_rep = explo_policy.tab_rep
         self.runner_kind = getattr(args, 'runner', 'native')
         self.sampling = getattr(args, 'sampling', 'host')
@@ -221,7 +232,7 @@ class PAACLearner(ActorLearner):
                 # kernels read env e's pushes in place at staging slots 4e..
                 # (fixed slots serve the native step's in-place reads; BAYESIAN steps in Python: compact staging)
                 fixed = self.sampling == 'device' and self.staging in ('zero_copy', 'pooled', 'resized') \
-                    and not self.bayes_bool
+                    and (not self.bayes_bool or self.bayes_native)
                 self.runners = NativeRunners(bank, self.workers, self.tab_rep, row_select=ROW_LUT,
                                              fixed_slots=fixed, pooled=self.staging == 'pooled',
                                              resized=self.staging == 'resized', col_lut=COL_LUT)
@@ -233,7 +244,7 @@ class PAACLearner(ActorLearner):
             if self.placement['pinned'] or self.placement['sliced']:  # ('slice': no worker cpus, the spin only)
                 self.runners.set_threads(self.placement['worker_cpus'], self.placement['spin_us'])
                 placement.apply_main(self.placement)
-            if self.sampling == 'device' and self.bayes_bool:
+            if self.sampling == 'device' and self.bayes_bool and not self.bayes_native:
                 if not self._native_note:
                     logging.info('BAYESIAN: no native macro-step; --sampling device runs the Python step with mt_sample')
                     self._native_note = True
@@ -281,9 +292,12 @@ class PAACLearner(ActorLearner):
             self.sync_h = torch.zeros(2, dtype=torch.int32, pin_memory=True)
             # the bootstrap chain stops at the dense slabs; the update's loss kernel finishes V(s_T)
             # (mt_returns_loss_backward_boot). MT_BOOT_IN_LOSS=0: the chain runs its heads kernel.
-            if not self.lstm_bool and os.environ.get('MT_BOOT_IN_LOSS', '1') != '0':
+            # (BAYESIAN: V(s_T) needs the dropout + fc4 stage, the chain always runs stage + heads)
+            if not self.lstm_bool and not self.bayes_bool and os.environ.get('MT_BOOT_IN_LOSS', '1') != '0':
                 flags |= _lib.MT_ROLLOUT_BOOT_SLABS
                 self._boot_ws = ws
+        if self.bayes_bool:
+            flags |= _lib.MT_ROLLOUT_DROPOUT
         self._bufs = _lib.mt_rollout_buffers(
             p(self.states), p(self.values), p(self.idx), p(self.pi_all), p(self.rep_all), p(ws), ws.numel(),
             p(self.counters), p(self.raw_d), src_rows, p(self.pair_d), p(self.pair_h), p(self.meta_d),
@@ -301,10 +315,10 @@ class PAACLearner(ActorLearner):
             _lib.check(_lib.hip().mt_rollout_set_policy(h, C.byref(self.policy)), 'mt_rollout_set_policy')
         self._over_dev = devnet.host_device_pointer(r.over) if self.lstm_bool else None
         self.boot_in_rollout = self.pipeline  # the last step's chain runs the bootstrap forward
-        # the rollout's stacking forward (pipelined, resized staging; NIPS, gray NATURE) also carries
+        # the rollout's stacking forward (pipelined, resized staging; NIPS, BAYESIAN, gray NATURE) also carries
         # slot T over into slot 0 at the next step 0 (mt_rollout_step): the update does not copy it
         self.slot0_in_rollout = self.pipeline and self.staging == 'resized' and not self.lstm_bool and (
-            self.network.arch == 'NIPS' or (self.network.arch == 'NATURE' and self.depth == 1))
+            self.network.arch in ('NIPS', 'BAYESIAN') or (self.network.arch == 'NATURE' and self.depth == 1))
         # the frame trunks' rollout steps stack in their conv1 launch (stack_conv1_kernel; slot 0 still
         # copied by the update)
         self.frame_stack_in_rollout = self.pipeline and self.staging == 'resized' and self.network.arch in ('PWYX', 'LSTM')
@@ -444,7 +458,10 @@ class PAACLearner(ActorLearner):
 
         BAYESIAN (always eager): bootstrap forward, mt_returns on the rollout's values, the train
         step's fresh mask (mt_dropout_redraw -> v', pi', rep'), mt_loss_backward on those with the
-        rollout's advantage, [whole-gradient all-reduce], mt_grad_sumsq + clip + RMSProp."""
+        rollout's advantage, [whole-gradient all-reduce], mt_grad_sumsq + clip + RMSProp.
+        With --bayes_native: [bootstrap forward unless the rollout ran it], the one-call backward
+        (mt_dropout_returns_loss_backward), clip + RMSProp, captured after the first eager update: one
+        graph the rollout's last step launches, or at world > 1 backward | eager all-reduce | apply."""
         self.book.drain()
         lr = self.get_lr()
         if self._update_in_rollout:  # the rollout's last step stored lr and launched the update graph
@@ -519,7 +536,7 @@ class PAACLearner(ActorLearner):
         self._launch_graph(g3, s)             # global-norm partials + clip + RMSProp
 
     def _graph_ok(self):
-        return (self.use_update_graph and self.profile is None and not self.bayes_bool
+        return (self.use_update_graph and self.profile is None and (not self.bayes_bool or self.bayes_native)
                 and self.native_step is not None and self.boot_in_rollout)
 
     def _update_backward(self):
@@ -530,7 +547,17 @@ class PAACLearner(ActorLearner):
             self._lstm_forward(T, self.v_boot)
         elif not self.lstm_bool and not boot_done:
             net.forward(self.states[T], E, out=(self.v_boot, self.pi_roll, self.rep_roll), ws_key='rollout', infer=True)
-        if self.lstm_bool or self.bayes_bool:
+        if self.bayes_native:
+            # redraw + n-step scan + loss + backward in one call: adv from the ROLLOUT's values, the critic
+            # and the loss terms from the redrawn v' (the loss kernel's RV variant)
+            end = self._mark('train_pass')
+            N = E * T
+            net.dropout_returns_loss_backward(self.states[:T].reshape(N, 84, 84, self.C), T, E, self.values,
+                                              self.idx[0].view(N), self.idx[1].view(N), self.rm_h_dev,
+                                              self.rm_h_dev + 4 * T * E, self.v_boot, self.gamma,
+                                              (self.v_upd, self.pi_upd, self.rep_upd), self.y, self.adv,
+                                              loss_terms=self.loss_terms, ws_key='train', norm_partials=not self.dp)
+        elif self.lstm_bool or self.bayes_bool:
             # (BAYESIAN: y and adv = y - the ROLLOUT's values, under the rollout's masks; the fused
             # returns + loss launch would feed one `values` to both the advantage and the critic)
             devnet.returns(self.rm_h_dev, self.rm_h_dev + 4 * T * E, self.values, self.v_boot, self.gamma, self.y,
@@ -578,7 +605,8 @@ class PAACLearner(ActorLearner):
     def _update_apply(self):
         T = self.max_local_steps
         # (the LSTM / fused-returns backwards leave the norm partials; BAYESIAN's mt_loss_backward does not)
-        self.network.apply_gradients(self.grad_scale, partials_ready=not self.dp and not self.bayes_bool)
+        self.network.apply_gradients(self.grad_scale,
+                                     partials_ready=not self.dp and (not self.bayes_bool or self.bayes_native))
         if self.lstm_bool:  # the next rollout's slots 0..4 = s_{T-4} .. s_T; windows carry over
             if T >= 5:
                 self.slots[0:5].copy_(self.slots[T:T + 5])
@@ -635,7 +663,7 @@ class PAACLearner(ActorLearner):
         self._buckets = None
         if not self.dp:  # one graph; the rollout's last step launches it (_register_update)
             graphs = capture([whole])
-        elif not self.lstm_bool and os.environ.get('MT_DP_BUCKETS', '1') != '0':
+        elif not self.lstm_bool and not self.bayes_bool and os.environ.get('MT_DP_BUCKETS', '1') != '0':
             # data parallel: the backward's first launches, up to the one that completes the dense /
             # head gradients (mt_net_backward_bucket_launches), then the rest (the conv backward); the
             # all-reduce of each gradient bucket runs on the all-reduce stream as soon as its launches
@@ -661,9 +689,11 @@ class PAACLearner(ActorLearner):
             if graphs is None:  # three graphs, the all-reduces issued between their replays
                 graphs = capture([window(0, k, self._update_backward), window(k, -1, self._update_backward),
                                   self._update_apply])
-        else:  # backward | all-reduce of the whole gradient | apply (LSTM, or MT_DP_BUCKETS=0)
+        else:  # backward | all-reduce of the whole gradient | apply (LSTM, BAYESIAN, or MT_DP_BUCKETS=0)
             graphs = None
-            if getattr(self.comm, 'capturable', False) and os.environ.get('MT_DP_ONE_GRAPH', '1') != '0':
+            # (BAYESIAN: always the two graphs around an eager all-reduce, its backward is not bucketed)
+            if getattr(self.comm, 'capturable', False) and os.environ.get('MT_DP_ONE_GRAPH', '1') != '0' \
+                    and not self.bayes_bool:
                 def one():  # a C-ABI communicator: the sum captured between the two (one graph)
                     self._update_backward()
                     self.comm.allreduce(self.network.grad)

@@ -2,7 +2,7 @@
 (train.py:1-130), driving the MI355X learner (manette_amd.paac.PAACLearner).
 
 Extra flags (this build only): --runner {native,python}, --sampling {host,device},
---staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed.
+--staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native.
 Multi-GPU: launch one process per GPU with torch.distributed.run; each rank trains
 -ec emulators of its own (--ec_scope rank, the default) or -ec / WORLD_SIZE of them (--ec_scope
 global: -ec 256 on 8 GPUs = 32 per GPU, BASELINE's "ec=256 sharded 8x32"); global env ids are
@@ -28,8 +28,15 @@ from manette_amd.exploration_policy import ExplorationPolicy
 logging.basicConfig(stream=sys.stdout, level=logging.DEBUG)
 
 
+def validate_args(args):
+    """Flag combinations that are refused, before any device allocation."""
+    from manette_amd.paac import check_arch_flags
+    check_arch_flags(args)
+
+
 def main(args):
     logging.debug('Configuration: {}'.format(args))
+    validate_args(args)
     _setup_distributed(args)
     logger_utils.save_args(args, args.debugging_folder)  # (per rank: rank r > 0 writes under rank<r>/)
     if args.sampling == 'host':
@@ -169,6 +176,10 @@ def get_arg_parser():
                         '(MT_ROLLOUT_PIPELINED, on by default)', dest='pipeline')
     parser.add_argument('--sampling', default='host', choices=['host', 'device'], help='host (default): numpy multinomial, the reference\'s stream (parity mode); device: the draw fused into the heads kernel (multinomial, or e-greedy with --egreedy / --epsilon / --annealed / --annealed_steps), the benchmarked native macro-step', dest='sampling')
     parser.add_argument('--ec_scope', default='rank', choices=['rank', 'global'], help='data parallel: -ec emulators per rank (rank, the reference\'s meaning for one process) or for the whole job, split evenly over WORLD_SIZE ranks (global)', dest='ec_scope')
+    parser.add_argument('--bayes_native', action='store_true', help='--arch BAYESIAN only: the native macro-step '
+                        '(with --sampling device and the native runner) and the update as one captured graph around '
+                        'the fused dropout backward (mt_dropout_returns_loss_backward); off: the Python step and the '
+                        'eager update', dest='bayes_native')
     parser.add_argument('--seed', default=0, type=int, help='parameter init / device sampling seed', dest='seed')
     parser.add_argument('--comm', default='rccl', choices=['rccl', 'torch'], help='data-parallel gradient all-reduce: '
                         'rccl = RCCL behind the C ABI (mt_allreduce, one GPU per rank); torch = torch.distributed on '
