@@ -198,6 +198,27 @@ class DeviceNetwork(object):
             out['mask'] = raw[off:off + n].reshape(hrows, -1).copy()
         return out
 
+    def backward_conv_grads(self, ws, layout, a, b=0):
+        """Diagnostics / parity: {'convK': dY} — the gradient of every conv layer's output that the
+        last backward left in the workspace (mt_net_workspace_region kind 3: [rows, OH, OW, C] fp32 at
+        full resolution, after the activation mask and, for a pooled layer, the MaxPoolGrad routing).
+        layout, a, b as forward_branches; layout 1 (the frame store): the backward covers rows
+        [0, 1 + (T + 4) E), the last E rows (s_T, read by the bootstrap only) are not written."""
+        raw = ws.cpu().numpy()
+        rows = {0: int(a), 1: 1 + (int(b) + 5) * int(a), 2: 5 * int(a)}[int(layout)]
+        convs = [v for v in self.vars if v[0].startswith('Network/conv') and v[0].endswith('_weights')]
+        out = {}
+        for i, (name, shape, _, _) in enumerate(convs):
+            cout = int(shape[3])
+            off, n = C.c_size_t(), C.c_size_t()
+            check(_lib.hip().mt_net_workspace_region(self._h, int(layout), int(a), int(b), 3, i, C.byref(off),
+                                                     C.byref(n)), 'mt_net_workspace_region')
+            side = int(round((n.value // 4 // (rows * cout)) ** 0.5))
+            assert rows * side * side * cout * 4 == n.value, (name, n.value, rows, cout)
+            out[name.split('/')[1]] = raw[off.value:off.value + n.value].view(np.float32).reshape(
+                rows, side, side, cout).copy()
+        return out
+
     # ---- BAYESIAN dropout (include/manette_hip.h) ----------------------------------------------
     def _ws_region(self, ws, batch, kind):
         off, n = C.c_size_t(), C.c_size_t()

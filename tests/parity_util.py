@@ -38,7 +38,7 @@ def check_grads(spec, got, G, loose, tight=2e-4, tie=5e-3):
 
 
 def device_branches(spec, P, frames, dev, act='relu', alpha=0.1, win=None, rows=None, chunk=32, tie=1e-5,
-                    near=2e-5):
+                    near=2e-5, exact=False):
     """The device's decisions at the gradient's discontinuities, checked, for the oracle to follow.
 
     dev = DeviceNetwork.forward_branches(...): per conv layer the stored post-activation output and
@@ -52,7 +52,22 @@ def device_branches(spec, P, frames, dev, act='relu', alpha=0.1, win=None, rows=
       device's branch (its stored output > 0, resp. >= 0) must equal the oracle's;
     closer than that, fp32 rounding may take either side, and the oracle then takes the device's
     (nets.*_loss_and_grads routes= / branches= / hbranch=), so the gradients are compared at the
-    tight bound. Returns dict(routes, branches, hbranch, ties, near)."""
+    tight bound. Returns dict(routes, branches, hbranch, ties, near).
+
+    exact=True adds the checks that need no threshold, at the points the rules above hand to the
+    device (structured frames put most windows there, tests/structured_frames.py):
+    - a pool window whose four receptive fields are identical in the input the DEVICE saw (the uint8
+      frames; the device's own pooled map of the layer before) is four times the same sum in the
+      same order, so it ties exactly on the device whatever the rounding: its argmax byte must be 0
+      in every channel (the first maximum in (row, col) order);
+    - where the fp64 pre-activation is exactly 0.0 the oracle's own rule stands (not positive for
+      relu; >= 0, slope 1, for leaky), the device's stored output must agree with it, and the
+      device's choice is not taken there.
+    The result then also has identical = {pooled conv: windows x channels checked} and zeros = the
+    number of exactly-zero pre-activations."""
+    if exact:
+        from structured_frames import identical_windows
+    identical, zeros = {}, 0
     pos = (lambda x: x > 0) if act == 'relu' else (lambda x: x >= 0)
     sel = (lambda a: a) if rows is None else (lambda a: a[rows])
     routes, branches, ties, nears = {}, {}, 0, 0
@@ -60,6 +75,7 @@ def device_branches(spec, P, frames, dev, act='relu', alpha=0.1, win=None, rows=
     for c0 in range(0, len(frames), chunk):
         flat, layers = nets.trunk_forward(spec, P, frames[c0:c0 + chunk], act, alpha)
         feats.append(flat)
+        prev_dev = None  # the device's stored output of the layer before (the next conv's input)
         for L in layers:
             y_dev, arg_dev = dev[L['name']]
             y_dev, arg_dev = sel(y_dev)[c0:c0 + chunk], None if arg_dev is None else sel(arg_dev)[c0:c0 + chunk]
@@ -75,9 +91,19 @@ def device_branches(spec, P, frames, dev, act='relu', alpha=0.1, win=None, rows=
                 ties += int((~clear).sum())
                 routes.setdefault(L['name'], []).append(arg_dev)
                 zq = nets.maxpool2(z)  # pre-activation of the window's maximum (act is monotonic)
+                if exact:
+                    same = identical_windows(frames[c0:c0 + chunk] if prev_dev is None else prev_dev, L['k'])
+                    bad = int((arg_dev[same] != 0).sum())
+                    assert bad == 0, (L['name'], c0, bad, int(same.sum()) * L['cout'],
+                                      'device max-pool argmax is not the first position on identical receptive fields')
+                    identical[L['name']] = identical.get(L['name'], 0) + int(same.sum()) * L['cout']
             else:
                 zq = z
+            prev_dev = y_dev
             far = np.abs(zq) >= near * zs
+            if exact:
+                far |= zq == 0
+                zeros += int((zq == 0).sum())
             bad = int(((pos(y_dev) != pos(zq)) & far).sum())
             assert bad == 0, (L['name'], c0, bad, 'device activation branch differs from the oracle away from 0')
             nears += int((~far).sum())
@@ -90,7 +116,13 @@ def device_branches(spec, P, frames, dev, act='relu', alpha=0.1, win=None, rows=
     hz = cache['hz']
     H_dev = dev['H'][:len(hz)]
     far = np.abs(hz) >= near * np.sqrt(np.mean(hz * hz))
+    if exact:
+        far |= hz == 0
+        zeros += int((hz == 0).sum())
     bad = int(((pos(H_dev) != pos(hz)) & far).sum())
     assert bad == 0, ('dense', bad, 'device activation branch differs from the oracle away from 0')
     nears += int((~far).sum())
-    return dict(routes=routes, branches=branches, hbranch=np.where(far, pos(hz), pos(H_dev)), ties=ties, near=nears)
+    out = dict(routes=routes, branches=branches, hbranch=np.where(far, pos(hz), pos(H_dev)), ties=ties, near=nears)
+    if exact:
+        out.update(identical=identical, zeros=zeros)
+    return out
