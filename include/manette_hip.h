@@ -631,6 +631,83 @@ int mt_graph_end(mt_stream_t stream, void **graph_exec);
 int mt_graph_launch(void *graph_exec, mt_stream_t stream);
 int mt_graph_destroy(void *graph_exec);
 
+/* ---- Catch: a device-resident environment (step, render and stack in one kernel) ------------
+ * A small real game whose state lives in HBM: a paddle, falling balls, lives, three actions. The
+ * counterpart of the reference's Catcher-v0 entry (pretrained/catcher/args.json), with rules of its
+ * own, integer arithmetic only, so the kernel, the host restatement (mt_catch_*_host) and a numpy
+ * restatement agree bit for bit. The rule:
+ *
+ *   field      84 x 84, background 0, x to the right, y down. The paddle is 12 wide and 3 high, rows
+ *              79..81, its left edge paddle_x in [0, 72]. The ball is 4 x 4, its top-left corner
+ *              (ball_x, ball_y), ball_x in [0, 80]. gray: ball 255, paddle 160; RGB: ball
+ *              (255, 64, 64), paddle (64, 255, 64). Where both cover a pixel the ball is drawn.
+ *   actions    0 = noop, 1 = left, 2 = right (num_actions = 3).
+ *   sub-frame  1. paddle_x += (action == 1 ? -2 : action == 2 ? +2 : 0), clamped to [0, 72];
+ *              2. ball_y += 2; ball_x += ball_dx; ball_x < 0: ball_x = -ball_x, ball_dx = -ball_dx;
+ *                 ball_x > 80: ball_x = 160 - ball_x, ball_dx = -ball_dx;
+ *              3. if ball_y + 3 >= 79 (the ball's bottom row has reached the paddle's top row): caught
+ *                 iff ball_x < paddle_x + 12 and ball_x + 4 > paddle_x: reward += 1; otherwise
+ *                 reward -= 1 and misses += 1. balls += 1. The episode is over iff misses >= lives or
+ *                 balls >= max_balls; otherwise a new ball spawns.
+ *   next(a)    4 sub-frames under action a; once the episode is over the remaining sub-frames of
+ *              that next are not played. A ball needs 38 sub-frames from its spawn to the paddle, so
+ *              the reward of a next is -1, 0 or +1. The observation FRAME of a next is the per-channel
+ *              maximum of the renders of the positions after sub-frames 3 and 4 (the frame-pool rule of
+ *              atari_emulator.py:79-100 at 84 x 84).
+ *   spawn      h = mix64(seed ^ mix64((global_env << 40) ^ ball_counter) ^ 0xCA7C4BA11D0FF1E5)
+ *              (mix64 and the nesting as in the sampler's uniforms, under a salt of its own);
+ *              ball_x = (h & 0xffffffff) % 81, ball_dx = ((h >> 32) % 3) - 1, ball_y = 0;
+ *              ball_counter += 1. ball_counter is per env and is not reset by a new game; global env
+ *              ids make a data-parallel shard draw what the union would draw.
+ *   new game   paddle_x = 36, misses = balls = 0, a spawn; then four next(0) whose rewards are dropped
+ *              (none can occur: 16 sub-frames) and whose four frames are the initial stacked state,
+ *              oldest first (get_initial_state of the reference's emulators).
+ *   macro-step (emulator_runner.py:24-41) next(a) is run tab_rep[r] + 1 times, the rewards summed,
+ *              stopping at the first episode end; after an episode end a new game starts at once and
+ *              the state returned is its initial state (all four stack positions replaced).
+ *   stacking   out[c] = prev[c + p] for c < 4 - p, else the (c - (4 - p))-th of the last p = min(pushes,
+ *              4) frames, as mt_preprocess; an episode end restarts the list of pushes with the new
+ *              game's four. RGB channel order [R_t0..R_t3, G_t0..G_t3, B_t0..B_t3]. */
+typedef struct mt_catch_config {
+  int32_t lives;     /* default 3 */
+  int32_t max_balls; /* default 20 */
+} mt_catch_config;
+/* Per-env state, 32 bytes, in caller-owned memory. */
+typedef struct mt_catch_state {
+  int32_t paddle_x, ball_x, ball_y, ball_dx, misses, balls;
+  uint64_t ball_counter;
+} mt_catch_state;
+
+/* A new game (ball_counter = 0 first) for envs env0 .. env0 + E - 1: state [E], out_state0
+ * [E][84][84][4*depth] = the stacked initial observation. MT_ERR_ARG before any launch for E < 1,
+ * env0 < 0, depth not 1 or 3, lives or max_balls < 1, or a null pointer. */
+int mt_catch_reset(const mt_catch_config *cfg, uint64_t seed, int env0, int E, int depth, mt_catch_state *state,
+                   uint8_t *out_state0, mt_stream_t stream);
+/* One macro-step of every env, one kernel: the game logic, the renders of the pushed frames and the
+ * next stacked state out [E][84][84][4*depth] from prev (no aliasing; prev is not read where all four
+ * positions are replaced). tab_rep: [R] int32 (device; an entry is used clamped to [0, 255]); a_idx,
+ * r_idx: [E] int32 (device), as the draw wrote them, used clamped to [0, 2] and [0, R - 1]. Writes
+ * reward_out [E] (the unclipped sum) and over_out [E] (1 or 0) as fp32, and into rm_out, a [2][T][E]
+ * fp32 buffer, rm_out[0][t][e] = the reward clipped to [-1, 1] and rm_out[1][t][e] = 1 - over (what
+ * mt_returns* read). frames_out / push_count_out (both or neither; may be NULL): the last p = min(pushes,
+ * 4) frames of env e at slots 4e .. 4e + p - 1 of frames_out [4E][84][84][depth], and p, in
+ * mt_preprocess_resized's layout (push_offset[e] = 4e). MT_ERR_ARG before any launch for bad sizes
+ * (E < 1, env0 < 0, R < 1, T < 1, t outside [0, T)), depth not 1 or 3, lives or max_balls < 1, out ==
+ * prev, or a null required pointer. */
+int mt_catch_step(const mt_catch_config *cfg, uint64_t seed, int env0, int E, int depth, const int32_t *tab_rep,
+                  int R, const int32_t *a_idx, const int32_t *r_idx, mt_catch_state *state, const uint8_t *prev,
+                  uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out, float *over_out,
+                  float *rm_out, int t, int T, mt_stream_t stream);
+/* The same rule for ONE env on HOST pointers; needs no GPU. The kernels are pinned against these.
+ * out_state0 / out (and then prev) / frames_out [4][84][84][depth] / push_count_out may be NULL:
+ * nothing is rendered for a NULL pointer (statistics runs). a and r are clamped as in the kernel. */
+int mt_catch_reset_host(const mt_catch_config *cfg, uint64_t seed, uint64_t global_env, int depth,
+                        mt_catch_state *state, uint8_t *out_state0);
+int mt_catch_step_host(const mt_catch_config *cfg, uint64_t seed, uint64_t global_env, int depth,
+                       const int32_t *tab_rep, int R, int a, int r, mt_catch_state *state, const uint8_t *prev,
+                       uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out,
+                       float *over_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,17 @@ class mt_policy(C.Structure):
                 ('annealing_steps', C.c_double), ('rows_per_call', C.c_int64)]
 
 
+class mt_catch_config(C.Structure):
+    """Catch (include/manette_hip.h): lives and balls of an episode."""
+    _fields_ = [('lives', C.c_int32), ('max_balls', C.c_int32)]
+
+
+class mt_catch_state(C.Structure):
+    """Per-env Catch state, 32 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ('paddle_x', 'ball_x', 'ball_y', 'ball_dx', 'misses', 'balls')] + \
+               [('ball_counter', C.c_uint64)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -135,6 +146,14 @@ _HIP_SIGS = {
     'mt_graph_end': (_I, [_P, C.POINTER(_P)]),
     'mt_graph_launch': (_I, [_P, _P]),
     'mt_graph_destroy': (_I, [_P]),
+    'mt_catch_reset': (_I, [C.POINTER(mt_catch_config), C.c_uint64, _I, _I, _I, _P, _P, _P]),
+    'mt_catch_step': (_I, [C.POINTER(mt_catch_config), C.c_uint64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                           _P, _P, _I, _I, _P]),
+    'mt_catch_reset_host': (_I, [C.POINTER(mt_catch_config), C.c_uint64, C.c_uint64, _I, C.POINTER(mt_catch_state),
+                                 _P]),
+    'mt_catch_step_host': (_I, [C.POINTER(mt_catch_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
+                                C.POINTER(mt_catch_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
+                                C.POINTER(_F)]),
 }
 
 _HOST_SIGS = {

@@ -20,17 +20,46 @@ MINIMAL_ACTIONS = {
 }
 
 
+# games with a device-resident environment (--runner device): the game lives in HBM, one kernel per macro-step
+DEVICE_GAMES = ('catch',)
+
+
+def has_device_env(game):
+    return str(game).lower() in DEVICE_GAMES
+
+
 class EnvironmentCreator(object):
     def __init__(self, args):
         game = args.game.lower()
         if game == 'tetris' or game.endswith('-v0'):
             raise NotImplementedError('gym / tetris emulators are out of scope (SURVEY.md §2)')
-        self.num_actions = MINIMAL_ACTIONS.get(game, 18)
+        self.game = game
         self.rgb = bool(getattr(args, 'rgb', False))
         self.rank_offset = int(getattr(args, 'env_id_offset', 0))
+        if game == 'catch':
+            # a real game (manette_amd/catch.py): the same rule on the host (CatchEmulator) and in HBM
+            # (create_device_env), both keyed on (--seed, global env id)
+            from . import catch
+            self.num_actions = catch.NUM_ACTIONS
+            self.catch_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
+                                   lives=int(getattr(args, 'catch_lives', catch.DEFAULT_LIVES)),
+                                   max_balls=int(getattr(args, 'catch_max_balls', catch.DEFAULT_MAX_BALLS)))
+            self.create_environment = lambda i: catch.CatchEmulator(self.rank_offset + i, **self.catch_args)
+            return
+        self.num_actions = MINIMAL_ACTIONS.get(game, 18)
         self.create_environment = lambda i: SyntheticEmulator(self.rank_offset + i, self.num_actions,
                                                               rgb=self.rgb)
 
+    def create_device_env(self, n_envs, tab_rep, device='cuda'):
+        """Envs [0, n_envs) of this rank (global ids offset by rank) as a device-resident environment."""
+        if not has_device_env(self.game):
+            raise ValueError('game %r has no device environment (--runner device serves: %s)'
+                             % (self.game, ', '.join(DEVICE_GAMES)))
+        from . import catch
+        return catch.CatchDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.catch_args)
+
     def create_bank(self, first_local, n_envs):
         """Native bank of envs [first_local, first_local+n) (global ids offset by rank)."""
+        if self.game in DEVICE_GAMES:
+            raise ValueError('game %r runs under --runner device or --runner python, not the native runner' % self.game)
         return SyntheticBank(self.rank_offset + first_local, n_envs, rgb=self.rgb)

@@ -11,6 +11,9 @@ Paths (args.runner):
             H2D from one pinned staging buffer and mt_preprocess builds the stacks (A2).
   'python'  reference-contract Python emulators (Runners / EmulatorRunner processes); finished
             84x84xC observations go H2D.
+  'device'  the game itself lives in HBM (-g catch, manette_amd/catch.py): one kernel per macro-step
+            steps, renders and stacks every env (mt_catch_step); with --sampling device a rollout is
+            T x (forward -> draw -> env kernel) enqueued without a host synchronisation (_device_rollout).
 Sampling (args.sampling): 'host' = the reference's numpy multinomial stream (parity mode),
 'device' = mt_sample (perf mode, same distribution), or with --egreedy / a test policy the e-greedy /
 argmax draw of mt_policy (mt_sample_policy, mt_rollout_set_policy), epsilon annealed on the device.
@@ -52,6 +55,19 @@ def check_arch_flags(args):
     --bayes_native switches the BAYESIAN arch to the native macro-step and the captured, fused update."""
     if getattr(args, 'bayes_native', False) and getattr(args, 'arch', None) != 'BAYESIAN':
         raise ValueError('--bayes_native is for --arch BAYESIAN (got --arch %s)' % getattr(args, 'arch', None))
+    # --runner device: the game lives in HBM (manette_amd/catch.py); games without a device env and the
+    # LSTM frame store are refused; a device game has no native (host-thread) bank
+    from .environment_creator import has_device_env
+    runner, game = getattr(args, 'runner', 'native'), getattr(args, 'game', 'pong')
+    if runner == 'device':
+        if not has_device_env(game):
+            raise ValueError('--runner device needs a game with a device environment (-g catch), got -g %s' % game)
+        if getattr(args, 'arch', None) == 'LSTM':
+            raise ValueError('--runner device does not serve --arch LSTM (its frame store is filled by the host path)')
+        if getattr(args, 'bayes_native', False):
+            raise ValueError('--runner device runs the BAYESIAN Python-step form: drop --bayes_native')
+    elif runner == 'native' and has_device_env(game):
+        raise ValueError('-g %s runs under --runner device or --runner python, not the native runner' % game)
 
 
 class PAACLearner(ActorLearner):
@@ -250,6 +266,17 @@ class PAACLearner(ActorLearner):
                     self._native_note = True
             elif self.sampling == 'device':
                 self._make_native_step()
+        elif self.runner_kind == 'device':
+            # the game lives in HBM: one kernel per macro-step advances every env, renders its pushed
+            # frames and writes states[t + 1]; clipped rewards and masks go to a device [2][T][E] buffer
+            # the update reads where it read the pinned one
+            T = self.max_local_steps
+            self.env = self.environment_creator.create_device_env(E, self.tab_rep, device=self.dev)
+            self.rm_d = torch.zeros(2, T, E, dtype=torch.float32, device=self.dev)
+            self.rm_h_dev = self.rm_d.data_ptr()
+            self.ro_d = torch.zeros(2, T, E, dtype=torch.float32, device=self.dev)  # [0] rewards, [1] over flags
+            self.ro_h = torch.zeros(2, T, E, dtype=torch.float32, pin_memory=True)
+            self.env.reset(self.states[0])
         else:
             emus = [self.environment_creator.create_environment(i) for i in range(E)]
             s0 = np.asarray([e.get_initial_state() for e in emus], dtype=np.uint8)
@@ -366,8 +393,36 @@ class PAACLearner(ActorLearner):
                                                  self._lib_ref(self._gs), devnet._stream()), 'mt_rollout_run')
             self.global_step = self._gs.value
             return
+        if self.runner_kind == 'device' and self.sampling == 'device':
+            return self._device_rollout()
         for t in range(self.max_local_steps):
             self.step(t)
+
+    def _device_rollout(self):
+        """Device env + device draw: T x (forward -> draw -> env kernel) enqueued with no host
+        synchronisation, then one D2H copy of the indices, rewards and over flags, one synchronisation,
+        and the bookkeeping of the T steps replayed in order (global_step, episode records, histograms as
+        step() leaves them). self.lockstep (tests, tools/catch_rate.py): synchronise after every step."""
+        net = self.network
+        E, T = self.emulator_counts, self.max_local_steps
+        lockstep = getattr(self, 'lockstep', False)
+        for t in range(T):
+            _, pi, rep = net.forward_rows(self.states[t], E, self.train_ws, T * E, t * E,
+                                          out=(self.values[t], self.pi_all[t], self.rep_all[t]), ws_key='rollout')
+            devnet.sample(pi, rep, self.sample_seed, self.counters, self.a_idx[t], self.r_idx[t], row0=self.env_offset,
+                          policy=self.policy)
+            self.env.step(self.a_idx[t], self.r_idx[t], self.states[t], self.states[t + 1], self.ro_d[0, t],
+                          self.ro_d[1, t], self.rm_d, t, T)
+            if lockstep:
+                torch.cuda.synchronize()
+        self.idx_h.copy_(self.idx, non_blocking=True)
+        self.ro_h.copy_(self.ro_d, non_blocking=True)
+        self.event.record()
+        self.event.synchronize()
+        a, r, ro = self.idx_h[0].numpy(), self.idx_h[1].numpy(), self.ro_h.numpy()
+        for t in range(T):
+            self.global_step = self.book.step(self.global_step, a[t], r[t], ro[0, t], ro[1, t],
+                                              self.rewards_h[t].numpy(), self.masks_h[t].numpy())
 
     def step(self, t):
         """One rollout macro-step (paac.py:140-205)."""
@@ -416,6 +471,13 @@ class PAACLearner(ActorLearner):
                 self._upload_pushes(total, self.states[t + 1], self.states[t])
             reward = self.runners.reward.numpy()
             over = self.runners.over.numpy()
+        elif self.runner_kind == 'device':  # the lockstep loop with the env kernel in place of the runner
+            self.env.step(self.a_idx[t], self.r_idx[t], self.states[t], self.states[t + 1], self.ro_d[0, t],
+                          self.ro_d[1, t], self.rm_d, t, self.max_local_steps)
+            self.ro_h[:, t].copy_(self.ro_d[:, t], non_blocking=True)
+            self.event.record()
+            self.event.synchronize()
+            reward, over = self.ro_h[0, t].numpy(), self.ro_h[1, t].numpy()
         else:
             sh = self.shared
             sh[3][...] = a

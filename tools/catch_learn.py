@@ -1,0 +1,108 @@
+"""Learning curve of the device-resident Catch (manette_amd/catch.py): NIPS, --runner device --sampling
+device, the hyper-parameters of the reference's pretrained/catcher run (lr 0.02 annealed over 3e8 steps,
+entropy 0.02, clip 3, gamma 0.99, T 5, ec 32). Per seed: the mean return of the last 100 finished
+episodes every --every updates, and the first update at which it reaches the bar = halfway between the
+uniform-random policy's mean return (host restatement, no rendering) and max_balls. The run is
+deterministic: counter-based draws, no float atomics. One JSON line per seed.
+
+  python tools/catch_learn.py --seeds 0 1 2 --max_updates 20000
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def random_policy_mean(episodes, lives, max_balls, seed=0):
+    """Mean return of uniform-random actions over `episodes` episodes of env 0 (mt_catch_step_host)."""
+    from manette_amd import _lib, catch
+    cfg = catch.config(lives, max_balls)
+    st = _lib.mt_catch_state()
+    catch.host_reset(cfg, seed, 0, 1, st)
+    rs = np.random.RandomState(12345)
+    tab = np.zeros(1, np.int32)
+    rets, ret = [], 0.0
+    while len(rets) < episodes:
+        rw, over, _ = catch.host_step(cfg, seed, 0, 1, tab, int(rs.randint(3)), 0, st)
+        ret += rw
+        if over:
+            rets.append(ret)
+            ret = 0.0
+    return float(np.mean(rets))
+
+
+def bar(lives, max_balls, episodes=100, seed=0):
+    return 0.5 * (random_policy_mean(episodes, lives, max_balls, seed) + max_balls)
+
+
+def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampling='device', max_rep=0, nb=1):
+    import train as cli
+    from manette_amd.exploration_policy import ExplorationPolicy
+    from manette_amd.paac import PAACLearner
+    a = cli.get_arg_parser().parse_args([])
+    a.game, a.arch, a.emulator_counts, a.emulator_workers = 'catch', arch, ec, 0
+    a.runner, a.sampling, a.seed = 'device', sampling, seed
+    a.max_repetition, a.nb_choices = max_rep, nb
+    a.catch_lives, a.catch_max_balls = lives, max_balls
+    a.initial_lr, a.lr_annealing_steps = 0.02, 300000000  # pretrained/catcher/args.json
+    a.debugging_folder = folder + '/'
+    a.max_global_steps = 1 << 40
+    a.checkpoint_interval = 1 << 40
+    explo = ExplorationPolicy(a)
+    nc, ec_ = cli.get_network_and_environment_creator(a, explo)
+    L = PAACLearner(nc, ec_, explo, a)
+    L.start()
+    return L
+
+
+def train_until(L, target, max_updates, every=0, window=100):
+    """Updates until the mean return of the last `window` finished episodes >= target (checked after
+    every update); returns (updates run, reached, curve [(update, mean)])."""
+    curve = []
+    for u in range(1, max_updates + 1):
+        L.book.new_update()
+        L.rollout()
+        L.update()
+        tr = L.book.total_rewards
+        mean = float(np.mean(tr[-window:])) if len(tr) >= window else None
+        if every and u % every == 0:
+            curve.append((u, mean))
+        if mean is not None and mean >= target:
+            curve.append((u, mean))
+            return u, True, curve
+    return max_updates, False, curve
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--seeds', type=int, nargs='+', default=[0, 1, 2])
+    ap.add_argument('--max_updates', type=int, default=20000)
+    ap.add_argument('--every', type=int, default=500)
+    ap.add_argument('--ec', type=int, default=32)
+    ap.add_argument('--lives', type=int, default=3)
+    ap.add_argument('--max_balls', type=int, default=20)
+    args = ap.parse_args()
+    import torch
+    target = bar(args.lives, args.max_balls)
+    for seed in args.seeds:
+        with tempfile.TemporaryDirectory() as tmp:
+            L = make_learner(tmp, seed, ec=args.ec, lives=args.lives, max_balls=args.max_balls)
+            t0 = time.time()
+            n, reached, curve = train_until(L, target, args.max_updates, args.every)
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            L.cleanup()
+        print(json.dumps(dict(seed=seed, bar=target, reached=reached, updates=n, seconds=round(dt, 2),
+                              env_steps=n * args.ec * 5, episodes=len(L.book.total_rewards),
+                              curve=[(u, None if m is None else round(m, 2)) for u, m in curve])), flush=True)
+
+
+if __name__ == '__main__':
+    main()

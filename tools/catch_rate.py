@@ -1,0 +1,110 @@
+"""Throughput of the device-resident Catch (manette_amd/catch.py).
+
+  kernel   mt_catch_step alone at E = 32 / 64, gray / RGB, R = 1 / 11, as a hipGraph of back-to-back
+           calls between device events (bench.graph_time), beside mt_preprocess_resized on the same
+           shapes and push counts: the stack traffic is the same, the game logic and the renders are the
+           difference.
+  rollout  env-steps/s of the learner (NIPS, ec 32, T 5, rollout + update) with the rollout enqueued
+           without a host synchronisation against the lockstep form (one after every step), the two
+           alternating in one process, three rounds.
+
+  python tools/catch_rate.py [--updates 300] [--skip_kernel] [--skip_rollout]
+One JSON line per measurement.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+
+def kernel_times(inner=50, reps=5):
+    import torch
+    import bench
+    from manette_amd import catch, network as devnet
+    for E in (32, 64):
+        for depth in (1, 3):
+            for R in (1, 11):
+                tab = [0] if R == 1 else [i for i in range(11)]
+                dev = catch.CatchDevice(E, tab, seed=1, rgb=depth == 3)
+                z = lambda *s, **k: torch.zeros(*s, device='cuda', **k)
+                bufs = [z(E, 84, 84, 4 * depth, dtype=torch.uint8), z(E, 84, 84, 4 * depth, dtype=torch.uint8)]
+                rs = np.random.RandomState(0)
+                a = torch.from_numpy(rs.randint(0, 3, E).astype(np.int32)).cuda()
+                r = torch.from_numpy(rs.randint(0, R, E).astype(np.int32)).cuda()
+                reward, over, rm = z(E), z(E), z(2, 1, E)
+                frames, count = z(4 * E, 84, 84, depth, dtype=torch.uint8), z(E, dtype=torch.int32)
+                off = torch.arange(0, 4 * E, 4, dtype=torch.int32, device='cuda')
+                dev.reset(bufs[0])
+                dev.step(a, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)  # the yardstick's pushes
+                k = [0]
+
+                def step():
+                    dev.step(a, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
+                    k[0] += 1
+
+                def stack():
+                    devnet.preprocess(frames, off, count, E, depth, None, None, bufs[k[0] & 1], bufs[1 - (k[0] & 1)],
+                                      resized=True)
+                    k[0] += 1
+
+                t_env = bench.graph_time(step, inner, reps)
+                t_stack = bench.graph_time(stack, inner, reps)
+                print(json.dumps(dict(what='kernel', E=E, depth=depth, R=R, mean_pushes=float(count.float().mean()),
+                                      catch_step_us=round(float(np.median(t_env)), 2),
+                                      preprocess_resized_us=round(float(np.median(t_stack)), 2),
+                                      catch_step_all=[round(x, 2) for x in t_env],
+                                      preprocess_resized_all=[round(x, 2) for x in t_stack])), flush=True)
+
+
+def rollout_rates(updates=300, rounds=3, ec=32):
+    import torch
+    from catch_learn import make_learner
+    with tempfile.TemporaryDirectory() as tmp:
+        L = make_learner(tmp, 0, ec=ec)
+        T = L.max_local_steps
+
+        def run(lockstep, n):
+            L.lockstep = lockstep
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                L.book.new_update()
+                L.rollout()
+                L.update()
+            torch.cuda.synchronize()
+            return n * T * ec / (time.perf_counter() - t0)
+
+        run(False, 20)
+        run(True, 20)
+        res = []
+        for _ in range(rounds):
+            res.append((run(False, updates), run(True, updates)))
+        L.cleanup()
+    print(json.dumps(dict(what='rollout', ec=ec, T=T, updates=updates,
+                          async_steps_per_s=[round(a) for a, _ in res], lockstep_steps_per_s=[round(b) for _, b in res],
+                          async_median=round(float(np.median([a for a, _ in res]))),
+                          lockstep_median=round(float(np.median([b for _, b in res]))))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--updates', type=int, default=300)
+    ap.add_argument('--skip_kernel', action='store_true')
+    ap.add_argument('--skip_rollout', action='store_true')
+    args = ap.parse_args()
+    if not args.skip_kernel:
+        kernel_times()
+    if not args.skip_rollout:
+        rollout_rates(args.updates)
+
+
+if __name__ == '__main__':
+    main()

@@ -1,8 +1,9 @@
 """Training CLI: the flags, defaults, args.json and signal handling of the reference's train.py
 (train.py:1-130), driving the MI355X learner (manette_amd.paac.PAACLearner).
 
-Extra flags (this build only): --runner {native,python}, --sampling {host,device},
---staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native.
+Extra flags (this build only): --runner {native,python,device}, --sampling {host,device},
+--staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native,
+--catch_lives, --catch_max_balls (-g catch: the device-resident game, manette_amd/catch.py).
 Multi-GPU: launch one process per GPU with torch.distributed.run; each rank trains
 -ec emulators of its own (--ec_scope rank, the default) or -ec / WORLD_SIZE of them (--ec_scope
 global: -ec 256 on 8 GPUs = 32 per GPU, BASELINE's "ec=256 sharded 8x32"); global env ids are
@@ -164,7 +165,9 @@ def get_arg_parser():
     parser.add_argument('--activation', default='relu', type=str, help="activation function for the network", dest="activation")
     parser.add_argument('--alpha_leaky_relu', default=0.1, type=float, help="coef for leaky relu", dest="alpha_leaky_relu")
     # this build
-    parser.add_argument('--runner', default='native', choices=['native', 'python'], help='native: C++ emulator threads + GPU preprocess; python: reference-contract emulator processes', dest='runner')
+    parser.add_argument('--runner', default='native', choices=['native', 'python', 'device'], help='native: C++ emulator threads + GPU preprocess; python: reference-contract emulator processes; device: the game lives in HBM, one kernel per macro-step steps, renders and stacks it (-g catch; not --arch LSTM)', dest='runner')
+    parser.add_argument('--catch_lives', default=3, type=int, help='-g catch: misses that end an episode', dest='catch_lives')
+    parser.add_argument('--catch_max_balls', default=20, type=int, help='-g catch: balls of an episode', dest='catch_max_balls')
     parser.add_argument('--staging', default='resized', choices=['in_place', 'zero_copy', 'copy', 'pooled', 'resized'],
                         help='native runner screens: each push\'s final 84x84 frame pooled + resized by the emulator '
                              'threads and read in place from pinned memory (resized), the GPU reading the emulators\' '
