@@ -160,7 +160,7 @@ __host__ __device__ __forceinline__ int choose_index(const float *p, int n, doub
   return best;
 }
 // One row's (a, r) under a policy from its counter value c: the standalone sample kernel and
-// mt_policy_draw_host (the fused heads kernel does the same over lanes, net.hip wave_choose).
+// mt_policy_draw_host (the fused heads kernel does the same over lanes, heads.h wave_choose).
 __host__ __device__ __forceinline__ void policy_row(const mt_policy &pol, const float *pa, int A, const float *pr,
                                                     int R, uint64_t seed, uint64_t global_row, uint64_t c, int *a,
                                                     int *r) {

@@ -1,6 +1,6 @@
 // Block-parallel jobs of the grouped launches (gemm.h launch_group) besides the GEMM products: the
 // fixed-order split-K slab sum, the global-norm partials, a conv weight gradient's bias-row sums and
-// the pair of two jobs as one. Shared by net.hip and tools/gemm_repro.hip.
+// the pair of two jobs as one. Shared by net.hip (with arch.h, heads.h, lstm.h) and tools/gemm_repro.hip.
 #pragma once
 #include "gemm.h"
 

@@ -1,5 +1,5 @@
 // LSTM arch (networks.py:227-258, Operations.rnn :112-127) on gfx950. Included by net.hip only
-// (uses its workspace/trunk helpers).
+// (uses its trunk and loss drivers, and the workspace helpers of arch.h).
 //
 // The memory window [B][5][84][84][C] is 5B frames, window-major (row b*5+t), that go through the
 // PWYX trunk (SAME convs + 2x2 pools, trunk_forward / trunk_backward of net.hip) to 6400
@@ -399,15 +399,15 @@ static int lstm_forward_impl(const mt_net *n, const float *P, const uint8_t *obs
 
 template <class Ar>
 static int lstm_backward_impl(const mt_net *n, const float *P, const uint8_t *obs, int B, float *ws,
-                              const float *pi, const float *rep, const float *v, const int32_t *a_idx,
-                              const int32_t *r_idx, const float *y, const float *adv, float beta, float *grad,
-                              float *loss_terms, hipStream_t s) {
+                              const LossArgs &la, hipStream_t s) {
   LstmWs X;
   const WsLayout L = lstm_ws_layout<Ar>(n, B, &X);
   const int rows = B * Ar::STEPS;
   const int act = n->cfg.activation;
   const float al = n->cfg.alpha_leaky;
-  MT_TRY(heads_backward<Ar>(n, P, B, ws, L, pi, rep, v, a_idx, r_idx, y, adv, beta, grad, loss_terms, s));
+  float *grad = la.grad;
+  MT_TRY(loss_bwd_launch<Ar>(n, P, B, ws, L, la, s));
+  MT_TRY(launch_group(s, head_wgrad_job<Ar>(n, B, ws, L, grad)));
   const float *Kx = P + n->off_lstm;
   const float *Kh = Kx + (size_t)Ar::FLAT * Ar::G4;
   const float *Wp = P + n->off_proj;
@@ -640,20 +640,15 @@ static int lstm_step_fwd_impl(const mt_net *n, const float *P, const uint8_t *fs
 
 template <class Ar>
 static int lstm_frames_bwd_impl(const mt_net *n, const float *P, const uint8_t *fstore, const int32_t *nz, int E,
-                                int T, float *ws, const float *pi, const float *rep, const float *v,
-                                const int32_t *a_idx, const int32_t *r_idx, const float *y, const float *adv,
-                                float beta, float *grad, float *loss_terms, hipStream_t s,
+                                int T, float *ws, const LossArgs &la, hipStream_t s,
                                 const NormOut &no = NormOut{}) {
   const LstmFrameWs X = lstm_frame_layout<Ar>(n, E, T);
   const WsLayout &L = X.L;
   const int W = T * E, rows = W * Ar::STEPS;
   const int act = n->cfg.activation;
   const float al = n->cfg.alpha_leaky;
-  if (sizeof(float) * ((size_t)W + 4 * 64) > 160 * 1024) {
-    set_error("batch %d exceeds the head-gradient LDS stage", W);
-    return MT_ERR_ARG;
-  }
-  MT_TRY(loss_bwd_launch<Ar>(n, P, W, ws, L, pi, rep, v, a_idx, r_idx, y, adv, beta, loss_terms, s));
+  float *grad = la.grad;
+  MT_TRY(loss_bwd_launch<Ar>(n, P, W, ws, L, la, s));
   const float *Kx = P + n->off_lstm;
   const float *Kh = Kx + (size_t)Ar::FLAT * Ar::G4;
   const float *Wp = P + n->off_proj;

@@ -1,1093 +1,13 @@
-// Policy/value network of the PAAC hot path on gfx950: parameter layout, forward (A5-A7) and
-// fused loss + backward (A10).
+// Policy/value network of the PAAC hot path on gfx950: forward (A5-A7) and fused loss + backward
+// (A10) as layer drivers over the architectures (arch.h), the heads and loss kernels (heads.h) and
+// the LSTM arch (lstm.h), then the C ABI.
 //
 // Reference: networks.py:130-278 (trunks), policy_v_network.py:19-74 (heads + loss).
-// Trunk products run on the fp32 MFMA GEMM core (gemm.h) with implicit im2col loaders; the
-// small heads (critic 1, actor A, repetition R outputs) and the loss are one workgroup per row.
-#include <string>
-#include <vector>
-#include <cmath>
-#include <algorithm>
-#include <tuple>
-
-#include "gemm.h"
-#include "jobs.h"
-#include "trunk_fused.h"
-#include "nips_bwd.h"
-#include "dconv.h"
-#include "nature_bwd.h"
-#include "bayes.h"
+// Trunk products run on the fp32 MFMA GEMM core (gemm.h) with implicit im2col loaders.
+#include "arch.h"
+#include "heads.h"
 
 namespace mt {
-
-// ---------------------------------------------------------------------------------------------
-// Architectures (compile-time geometry). C = 4*depth input channels. Layers = tuple of conv
-// geometries; POOL bitmask = layers followed by a 2x2/2 VALID max pool (networks.py:108-110).
-// ---------------------------------------------------------------------------------------------
-template <int C>
-struct NipsArch {  // networks.py:178-192
-  using Layers = std::tuple<ConvGeom<C, 16, 8, 4, 84, 84, false>, ConvGeom<16, 32, 4, 2, 20, 20, false>>;
-  static constexpr int NCONV = 2;
-  static constexpr unsigned POOL = 0;
-  static constexpr int FLAT = 9 * 9 * 32;  // 2592
-  static constexpr int F = 256;
-  static constexpr const char *FC = "fc3";
-  static constexpr int FUSED_SLABS = FusedNips<C>::FC_SPLITS;  // inference forward: trunk_fused.h
-  static constexpr int FC_ROWS = 0;                         // (the fused trunk has its own dense kernel)
-  static constexpr bool LSTM = false;
-  static constexpr int DROP_F = 0;
-};
-// networks.py:194-204: the NIPS trunk, then tf.nn.dropout(fc3) -> fc4 256 -> 256 (bayes.h) under the
-// heads. NIPS geometry, so the fused inference trunk and the fused gray conv backward apply unchanged.
-template <int C>
-struct BayesArch : NipsArch<C> {
-  static constexpr int DROP_F = kDropF;  // the extra stage: dropout over fc3's features + fc4
-  static_assert(NipsArch<C>::F == kDropF, "dropout_fc_kernel is built for 256 features");
-};
-template <int C>
-struct NatureArch {  // networks.py:261-278
-  using Layers = std::tuple<ConvGeom<C, 32, 8, 4, 84, 84, false>, ConvGeom<32, 64, 4, 2, 20, 20, false>,
-                            ConvGeom<64, 64, 3, 1, 9, 9, false>>;
-  static constexpr int NCONV = 3;
-  static constexpr unsigned POOL = 0;
-  static constexpr int FLAT = 7 * 7 * 64;  // 3136
-  static constexpr int F = 512;
-  static constexpr const char *FC = "fc4";
-  static constexpr int FUSED_SLABS = 0;  // no fused inference trunk: layered path
-  static constexpr int FC_ROWS = 7;      // dense layer by conv3 rows (row_fc_kernel)
-  // its K-splits (= slabs): 8, 512 blocks at E = 32 / 64 (two per CU) instead of 7 rows' 448
-  // (Breakout isolated step forward 39.5 -> 38.5 us; 4 splits, 256 blocks: slower; profiles/r06fcs)
-  static constexpr int FC_SPLITS = 8;
-  static constexpr bool LSTM = false;
-  static constexpr int DROP_F = 0;
-};
-template <int C>
-struct PwyxArch {  // networks.py:206-225: SAME convs, 2x2 pools after conv1-3
-  using Layers = std::tuple<ConvGeom<C, 32, 5, 1, 84, 84, true>, ConvGeom<32, 32, 5, 1, 42, 42, true>,
-                            ConvGeom<32, 64, 4, 1, 21, 21, true>, ConvGeom<64, 64, 3, 1, 10, 10, true>>;
-  static constexpr int NCONV = 4;
-  static constexpr unsigned POOL = 0x7;
-  static constexpr int FLAT = 10 * 10 * 64;  // 6400
-  static constexpr int F = 512;
-  static constexpr const char *FC = "fc5";
-  static constexpr int FUSED_SLABS = 0;
-  static constexpr int FC_ROWS = 10;  // dense layer by conv4 rows (row_fc_kernel)
-  static constexpr int FC_SPLITS = 8;  // its K-splits: 512 blocks at E = 32 (10: 640), as NATURE's
-  static constexpr bool LSTM = false;
-  static constexpr int DROP_F = 0;
-};
-
-template <class Ar, int I>
-using LayerG = std::tuple_element_t<I, typename Ar::Layers>;
-
-// gray NATURE: the rollout chain stacks in conv1 and runs its convs as one dataflow launch
-// (dconv.h nature_chain_kernel)
-template <class Ar>
-constexpr bool nature_stacking() {
-  if constexpr (Ar::LSTM || Ar::NCONV != 3) return false;
-  else return LayerG<Ar, 0>::CIN == 4 && !LayerG<Ar, 0>::SAME;
-}
-
-// The NIPS gray trunk's conv backward as one launch of per-image workgroups (nips_bwd.h) instead of
-// the layered trunk_backward.
-// Its slabs are per image (257 x 16 floats each, summed serially per column), so above this batch
-// the layered trunk_backward (split-K slabs capped at kSlabFloats) takes over: at the benchmarked
-// batches (N = E * T <= 1,280) the fused form's two slab regions stay <= 21 MB each.
-constexpr int kNipsFusedBwdMaxRows = 1280;
-template <class Ar>
-constexpr bool nips_fused_bwd() {
-  if constexpr (Ar::LSTM || Ar::NCONV != 2 || Ar::FUSED_SLABS == 0) return false;
-  else return LayerG<Ar, 0>::CIN == 4;
-}
-template <class Ar, int I>
-constexpr bool pooled() {
-  return (Ar::POOL >> I) & 1u;
-}
-// the frame trunks (PWYX, LSTM; gray or RGB): the rollout step's conv1 launch pulls + stacks each
-// env as it is published (dconv.h stack_conv1_kernel), conv2 .. layered
-template <class Ar>
-constexpr bool frame_stacking() {
-  using G = LayerG<Ar, 0>;
-  return G::S == 1 && G::SAME && pooled<Ar, 0>() && (G::CIN == 4 || G::CIN == 12) && G::H == 84 && G::W == 84;
-}
-// spatial size of layer I's output after its (optional) pool
-template <class Ar, int I>
-constexpr int out_hw() {
-  using G = LayerG<Ar, I>;
-  return pooled<Ar, I>() ? G::OH / 2 : G::OH;
-}
-
-}  // namespace mt
-
-struct VarInfo {
-  std::string name;
-  int ndim;
-  int64_t shape[4];
-  size_t offset;
-  float bound;
-};
-
-struct mt_net {
-  mt_net_config cfg;
-  int C;       // input channels (4*depth)
-  int F;       // trunk feature width
-  int O;       // 1 + A + R head outputs
-  int nconv;
-  int flat;
-  std::vector<VarInfo> vars;
-  size_t nparams;
-  size_t off_conv[4];  // weights offset of each conv (biases follow)
-  size_t off_fc, off_critic, off_actor, off_rep;
-  size_t off_lstm = 0, off_proj = 0;  // LSTM arch: cell kernel (+bias), projection w (+b)
-  size_t off_fc4 = 0;                 // BAYESIAN arch: fc4 weights (biases follow)
-};
-
-namespace mt {
-
-static size_t align64(size_t x) { return (x + 63) & ~size_t(63); }
-
-static void add_named_pair(mt_net *n, size_t &off, const std::string &wname, const std::string &bname,
-                           std::vector<int64_t> wshape, int64_t nb, float bw, float bb, size_t *woff) {
-  off = align64(off);
-  VarInfo w{};
-  w.name = wname;
-  w.ndim = (int)wshape.size();
-  size_t ws = 1;
-  for (int i = 0; i < w.ndim; ++i) {
-    w.shape[i] = wshape[i];
-    ws *= (size_t)wshape[i];
-  }
-  w.offset = off;
-  w.bound = bw;
-  VarInfo b{};
-  b.name = bname;
-  b.ndim = 1;
-  b.shape[0] = nb;
-  b.offset = off + ws;
-  b.bound = bb;
-  *woff = off;
-  n->vars.push_back(w);
-  n->vars.push_back(b);
-  off = off + ws + (size_t)nb;
-}
-
-static void add_pair(mt_net *n, size_t &off, const std::string &scope, const std::string &nm,
-                     std::vector<int64_t> wshape, int64_t nb, float bw, float bb, size_t *woff) {
-  add_named_pair(n, off, scope + "/" + nm + "/" + nm + "_weights", scope + "/" + nm + "/" + nm + "_biases",
-                 std::move(wshape), nb, bw, bb, woff);
-}
-
-template <class G>
-static void add_conv(mt_net *n, size_t &off, int idx) {
-  // networks.py:34-55: weights U(+-1/sqrt(filters*k*k)) (shape[3] is the OUTPUT channel count),
-  // biases U(+-1/sqrt(in_channels*k*k)).
-  const float bw = (float)(1.0 / std::sqrt((double)(G::COUT * G::KH * G::KW)));
-  const float bb = (float)(1.0 / std::sqrt((double)(G::CIN * G::KH * G::KW)));
-  std::string nm = "conv" + std::to_string(idx + 1);
-  add_pair(n, off, "Network", nm, {G::KH, G::KW, G::CIN, G::COUT}, G::COUT, bw, bb,
-           &n->off_conv[idx]);
-}
-
-template <class Ar, int I = 0>
-static void add_convs(mt_net *n, size_t &off) {
-  if constexpr (I < Ar::NCONV) {
-    add_conv<LayerG<Ar, I>>(n, off, I);
-    add_convs<Ar, I + 1>(n, off);
-  }
-}
-
-template <class Ar>
-static void add_heads(mt_net *n, size_t &off) {
-  const float bh = (float)(1.0 / std::sqrt((double)Ar::F));
-  const int A = n->cfg.num_actions, R = n->cfg.num_reps;
-  // policy_v_network.py:22 (critic), :31 (actor), :47 (repetition) — TF creation order.
-  add_pair(n, off, "Training/Critic", "critic_output", {Ar::F, 1}, 1, bh, bh, &n->off_critic);
-  add_pair(n, off, "Training/Actor", "actor_output", {Ar::F, A}, A, bh, bh, &n->off_actor);
-  add_pair(n, off, "Training/Repetition", "repetition_output", {Ar::F, R}, R, bh, bh, &n->off_rep);
-}
-
-template <class Ar>
-static void build_layout(mt_net *n) {
-  static_assert(out_hw<Ar, Ar::NCONV - 1>() * out_hw<Ar, Ar::NCONV - 1>() *
-                    LayerG<Ar, Ar::NCONV - 1>::COUT == Ar::FLAT, "flatten width");
-  size_t off = 0;
-  add_convs<Ar>(n, off);
-  const float bf = (float)(1.0 / std::sqrt((double)Ar::FLAT));  // networks.py:72-89
-  add_pair(n, off, "Network", Ar::FC, {Ar::FLAT, Ar::F}, Ar::F, bf, bf, &n->off_fc);
-  if constexpr (Ar::DROP_F > 0) {
-    // fc4 is built inside a second `with tf.name_scope('Network')`, which TF 1.x uniquifies to
-    // Network_1 (TF's published behaviour; no BAYESIAN checkpoint pins it, as for the LSTM names)
-    const float b4 = (float)(1.0 / std::sqrt((double)Ar::DROP_F));
-    add_named_pair(n, off, "Network_1/fc4/fc4_weights", "Network_1/fc4/fc4_biases", {Ar::DROP_F, Ar::F}, Ar::F, b4,
-                   b4, &n->off_fc4);
-  }
-  add_heads<Ar>(n, off);
-  n->nparams = align64(off);
-  n->F = Ar::F;
-  n->flat = Ar::FLAT;
-  n->nconv = Ar::NCONV;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Workspace layout (floats), a pure function of (net, batch).
-// ---------------------------------------------------------------------------------------------
-struct WsLayout {
-  // per conv layer: act = post-activation conv output (unpooled layers), pool = pooled output and
-  // parg = its window argmax bytes (pooled layers: the conv epilogue pools, EpBiasActPool), dact =
-  // the gradient of the conv output (pre-activation after masking; full resolution)
-  size_t act[4], pool[4], parg[4], dact[4], fcslab, H, dz, dH, wslab, wslab2, total;
-  size_t sync;  // the stacking chains' counters (nature_chain_kernel, stack_conv1_kernel; u32, zero between launches)
-  // BAYESIAN (bayes.h): fc3's output, the mask bytes, the dropped features D, fc4's one-slab product,
-  // fc3's output gradient and the dropout state {seed, row0, counters[B]} (uint64)
-  size_t H3 = 0, mask = 0, D = 0, z4 = 0, dz3 = 0, dstate = 0;
-  int fc_splits;
-};
-
-template <int N, int BK>
-struct TileFor {
-  using T = Tile<64, 64, 2, 2, BK>;
-};
-// Thin-N conv tiles (COUT or CIN of 16 / 32): the 4 waves split M, one 16-row fragment each
-// (128 / 256-row thin tiles measured slower). BK is capped so the A stage stays <= 96 KB.
-constexpr int kThinBM = 64;
-constexpr int thin_bk(int bk) { return kThinBM * (bk + 4) * 4 > 98304 && bk % 32 == 0 ? thin_bk(bk / 2) : bk; }
-template <int BK>
-struct TileFor<16, BK> {
-  using T = Tile<kThinBM, 16, 4, 1, thin_bk(BK)>;
-};
-template <int BK>
-struct TileFor<32, BK> {
-  using T = Tile<kThinBM, 32, 4, 1, thin_bk(BK)>;
-};
-
-// K-chunk of a forward conv: the whole K when it fits 256, else the largest of 256/192/128
-// dividing it (one fill per chunk, all loads of a chunk in flight together).
-template <int K>
-constexpr int conv_bk() {
-  return K <= 256 ? ((K + 15) / 16) * 16 : (K % 256 == 0 ? 256 : (K % 192 == 0 ? 192 : 128));
-}
-
-template <class G>
-using TileConvFwd = typename TileFor<G::COUT, conv_bk<G::KK>()>::T;
-template <class G>
-using TileConvWgrad = typename TileFor<G::COUT, 64>::T;
-// dX: BK 64 = half the LDS of 128, twice the resident workgroups (LSTM conv2 dX -5 %, Pong conv2 dX -7 %);
-// 32 for the 64-channel inputs (LSTM conv4 group 59.6 -> 56.1 us, NATURE conv3 39.6 -> 38.7; the thin
-// CIN-32 tile is slower at 32: LSTM conv3 181.6 -> 190.8, profiles/r06dg)
-template <class G>
-using TileConvDgrad = typename TileFor<G::CIN, G::CIN >= 64 ? 32 : 64>::T;
-
-using TileFc = Tile<32, 64, 2, 2, 64>;       // dense forward, M = batch (small), split-K
-// dense dW (GEMM-K = batch: 160 = 2 chunks at ec=32) and dX (GEMM-K = F, M = batch): latency-bound
-// at rollout batches, so small tiles — more workgroups, fewer MFMAs per wave (Pong: dense group
-// 12.1 -> 10.6 us; LSTM dense dW 17.1 -> 13.1 us)
-using TileDenseW = Tile<32, 64, 2, 2, 80>;
-using TileDenseX = Tile<32, 32, 2, 2, 128>;
-
-static int pick_splits(int grid_mn, int K, int bk, int target = 512) {
-  int s = target / (grid_mn > 0 ? grid_mn : 1);
-  if (s < 1) s = 1;
-  const int chunks = cdiv(K, bk);
-  if (s > chunks) s = chunks;
-  return s;
-}
-
-// K splits of a conv weight gradient (GEMM-K = B*OH*OW, tiny M x N): enough that a block walks
-// at most kWgradChunks BK-chunks (each chunk is one load latency: with only M x N / 1024 MFMA
-// tiles per wave the chunk chain, not the MFMA, sets a block's time), capped so the partial slabs
-// stay <= kSlabFloats.
-// (4 K-chunks of 64 per block: re-checked against 1, 2, 8, 16 — DESIGN §8)
-constexpr int kWgradChunks = 4;
-constexpr size_t kSlabFloats = (size_t)4 << 20;
-template <class G>
-static int conv_wgrad_splits(int B) {
-  using T = TileConvWgrad<G>;
-  const int M = G::KK + 1;
-  const int K = B * G::OH * G::OW;
-  int s = std::max(pick_splits(cdiv(M, T::BM) * cdiv(G::COUT, T::BN), K, T::BK), cdiv(cdiv(K, T::BK), kWgradChunks));
-  s = std::min<int>(s, (int)std::max<size_t>(kSlabFloats / ((size_t)M * G::COUT), 1));
-  return gemm_splits<T>(K, s);
-}
-
-template <class G>
-static size_t conv_wgrad_slab(int B) {
-  const int s = conv_wgrad_splits<G>(B);
-  const size_t generic = s > 1 ? (size_t)s * (G::KK + 1) * G::COUT : 0;
-  if constexpr (dconv_wgrad<G>())  // direct weight gradient (dconv.h)
-    return std::max(generic, dwgrad_slab_floats<G, false>(B));
-  return generic;
-}
-
-template <class Ar>
-static int fc_splits(int B, int F) {
-  if constexpr (Ar::FC_ROWS > 0) return Ar::FC_SPLITS;  // row_fc_kernel's K-splits
-  const int s = pick_splits(cdiv(B, TileFc::BM) * cdiv(F, TileFc::BN), Ar::FLAT, TileFc::BK, 128);
-  return gemm_splits<TileFc>(Ar::FLAT, s);
-}
-
-// The dense layer's partial slabs [splits][B][F] of the inference forwards: the row-split kernel
-// (trunk_fused.h row_fc_kernel: one slab per conv output row, one memory round trip per block)
-// where the arch has FC_ROWS, else the split-K GEMM. advance: the replayed rollout graph's
-// sequence bases (row_fc_kernel's block 0).
-template <class Ar>
-static int launch_fc(const float *flat, int B, const float *Wfc, float *slabs, int splits, hipStream_t s,
-                     uint32_t *advance = nullptr, uint32_t advance_by = 0) {
-  if constexpr (Ar::FC_ROWS > 0)
-    return launch_row_fc<Ar::FLAT / Ar::FC_ROWS, Ar::FC_ROWS, Ar::F, Ar::FC_SPLITS>(flat, B, Wfc, slabs, s, advance,
-                                                                                  advance_by);
-  else
-    return launch_gemm<TileFc>(LdRowMajor{flat, Ar::FLAT}, LdColMajor{Wfc, Ar::F, -1}, EpSlab{slabs, B, Ar::F}, B,
-                               Ar::F, Ar::FLAT, splits, s);
-}
-
-template <class Ar, int I = 0>
-static void ws_layers(WsLayout &L, size_t &off, int B, size_t &wslab) {
-  if constexpr (I < Ar::NCONV) {
-    using G = LayerG<Ar, I>;
-    auto take = [&](size_t nf) {
-      size_t o = off;
-      off = align64(off + nf);
-      return o;
-    };
-    const size_t a = (size_t)B * G::OH * G::OW * G::COUT;
-    const size_t p = pooled<Ar, I>() ? (size_t)B * (G::OH / 2) * (G::OW / 2) * G::COUT : 0;
-    L.act[I] = take(pooled<Ar, I>() ? 0 : a);
-    L.dact[I] = take(a);
-    L.pool[I] = take(p);
-    L.parg[I] = take(p / 4);  // bytes (COUT % 4 == 0)
-    wslab = std::max(wslab, conv_wgrad_slab<G>(B));
-    ws_layers<Ar, I + 1>(L, off, B, wslab);
-  }
-}
-
-struct LstmWs;
-template <class Ar>
-static WsLayout lstm_ws_layout(const mt_net *n, int B, LstmWs *X);  // lstm.h
-
-template <class Ar>
-static WsLayout ws_layout(const mt_net *n, int B) {
-  if constexpr (Ar::LSTM) return lstm_ws_layout<Ar>(n, B, nullptr);
-  WsLayout L{};
-  size_t off = 0;
-  auto take = [&](size_t nf) {
-    size_t o = off;
-    off = align64(off + nf);
-    return o;
-  };
-  size_t wslab = 0;
-  ws_layers<Ar>(L, off, B, wslab);
-  if constexpr (nips_fused_bwd<Ar>())  // per-image conv1 slabs (wslab), per-pair conv2 slabs (wslab2)
-    if (B <= kNipsFusedBwdMaxRows)
-      wslab = std::max(wslab, std::max((size_t)B * NipsConvBwdJob::SLAB1, (size_t)((B + 1) / 2) * NipsConvBwdJob::SLAB2));
-  L.fc_splits = fc_splits<Ar>(B, Ar::F);
-  L.fcslab = take((size_t)std::max(L.fc_splits, Ar::FUSED_SLABS) * B * Ar::F);
-  L.H = take((size_t)B * Ar::F);
-  L.dz = take((size_t)B * n->O);
-  L.dH = take((size_t)B * Ar::F);
-  L.wslab = take(wslab);
-  L.wslab2 = take(wslab);  // ping-pong slab regions of consecutive conv layers (trunk_backward)
-  if constexpr (Ar::DROP_F > 0) {
-    L.H3 = take((size_t)B * Ar::DROP_F);
-    L.mask = take((size_t)B * Ar::DROP_F / 4);  // bytes
-    L.D = take((size_t)B * Ar::DROP_F);
-    L.z4 = take((size_t)B * Ar::F);
-    L.dz3 = take((size_t)B * Ar::DROP_F);
-    L.dstate = take(2 * (size_t)(2 + B));  // uint64 words
-  }
-  // the rollout chains' counters (nature_chain_kernel; stack_conv1_kernel), zero between launches
-  L.sync = take(nature_stacking<Ar>() ? (size_t)kChainSyncWords * B
-                                      : frame_stacking<Ar>() && !Ar::LSTM ? (size_t)stack_conv1_sync_words(B) : 0);
-  L.total = off;
-  return L;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Kernels: slab sum, heads forward, loss + heads backward, heads weight gradient.
-// ---------------------------------------------------------------------------------------------
-static int sum_slabs(const float *P, int S, size_t n, float *out, hipStream_t s) {
-  return launch_group(s, SlabJob{P, S, n, out});
-}
-
-struct HeadParams {
-  const float *Wc, *bc, *Wa, *ba, *Wr, *br;
-  int A, R, F;
-  int nq;  // f32x4 quads of the head region [Wc, end of the parameters): critic | actor | repetition
-};
-
-// The three head (weights, biases) pairs are the last variables of every layout (add_heads), each
-// 64-float aligned, so [Wc, P + nparams) is one contiguous 256-B-aligned region.
-static HeadParams head_params(const mt_net *n, const float *P) {
-  HeadParams h;
-  h.F = n->F;
-  h.A = n->cfg.num_actions;
-  h.R = n->cfg.num_reps;
-  h.Wc = P + n->off_critic;
-  h.bc = h.Wc + h.F;
-  h.Wa = P + n->off_actor;
-  h.ba = h.Wa + (size_t)h.F * h.A;
-  h.Wr = P + n->off_rep;
-  h.br = h.Wr + (size_t)h.F * h.R;
-  h.nq = (int)((n->nparams - n->off_critic) / 4);
-  return h;
-}
-
-// Head output o (0 = critic, 1..A = actor, 1+A.. = repetition) inside the head region staged in
-// LDS (heads_row): offset of its weight for feature 0, the feature stride, and its bias.
-__device__ __forceinline__ void head_col_lds(const HeadParams &hp, int o, int &base, int &stride, int &bias) {
-  // selects only (no branches): o is wave-uniform, so these are a few scalar instructions
-  const int oa = (int)(hp.Wa - hp.Wc), orr = (int)(hp.Wr - hp.Wc);
-  const bool c = o == 0, a = o <= hp.A;
-  const int k = a ? o - 1 : o - 1 - hp.A;  // column within the actor / repetition block
-  const int w0 = a ? oa : orr, st = a ? hp.A : hp.R;
-  base = c ? 0 : w0 + k;
-  stride = c ? 1 : st;
-  bias = c ? hp.F : w0 + hp.F * st + k;
-}
-
-// Softmax over n logits held in lanes [0, n) of one wave (x/temp, TF: exp(x-max)/sum).
-__device__ __forceinline__ float wave_softmax(float x, int lane, int n) {
-  const float xm = lane < n ? x : -INFINITY;
-  const float mx = wave_max(xm);
-  const float e = lane < n ? expf(x - mx) : 0.f;
-  const float s = wave_sum(e);
-  return e / s;
-}
-
-constexpr int kMaxHeads = 64;  // 1 + A + R <= 64
-constexpr int kMaxScan = 1024;  // max t_max of the fused n-step scan (mt_returns_loss_backward)
-// Dynamic LDS the heads and loss kernels may ask for: the largest head region mt_net_create accepts
-// (F = 512, A = 32, R = 31: 64 outputs x 513 rows, each (w, b) pair 64-float aligned = 131,840 bytes).
-// With loss_bwd_kernel's ~10.5 KB of static LDS (the scan buffer, the bootstrap's features) that stays
-// inside the 160 KB of a CU; a cap of 150 KB did not, and hipFuncSetAttribute refused it (invalid
-// argument), so no head region above 64 KB could run the loss kernel.
-constexpr size_t kHeadRegionMaxBytes = 132 * 1024;
-
-// draw_index (common.h) over probabilities held in lanes [0, n): same order and rounding.
-__device__ __forceinline__ int wave_draw(float p, int n, double u) {
-  const double epsneg = 5.9604644775390625e-08;
-  double cum = 0.0;
-  int res = n - 1;
-  for (int j = 0; j < n - 1; ++j) {
-    const float pj = lane_f(p, j);  // (j is wave-uniform: a readlane, not an LDS-routed shuffle)
-    cum += (double)(pj - (float)epsneg);
-    if (res == n - 1 && u < cum) res = j;
-  }
-  return res;
-}
-// choose_index (common.h) over probabilities held in lanes [0, n): the e-greedy / argmax chooser. The
-// first-maximum search walks n readlanes, as wave_draw does: values and the running best are
-// wave-uniform, so the walk is scalar compares and selects.
-__device__ __forceinline__ int wave_choose(float p, int n, double u, double eps) {
-  float bv = lane_f(p, 0);
-  int best = 0;
-  for (int j = 1; j < n; ++j) {
-    const float pj = lane_f(p, j);
-    if (argmax_takes(bv, pj)) {
-      best = j;
-      bv = pj;
-    }
-  }
-  return u < eps ? explore_index(n, u, eps) : best;
-}
-
-// One workgroup per row b (NT / 64 waves: 4 for F <= 256, 8 for F <= 512):
-//  1. h = act(sum_z slabs[z][b] + b_fc) — the split-K dense layer finished here
-//     (networks.py:57-70); every thread owns F/NT features;
-//  2. logits_o = [h, 1] . W_o for the 1+A+R head outputs (policy_v_network.py:22, :31, :47):
-//     wave w takes outputs o = w, w + NW, ...; lanes split F and reduce with DPP;
-//  3. wave 0: v = logit_0, pi = softmax(logits_A / temp), rep = softmax(logits_R / temp);
-//  4. rollout path (smp.counters != null): wave 0 draws (a, r) for the row (A3, common.h).
-// Latency is everything here (32 blocks at E = 32, on the macro-step's critical chain), so every
-// global load is issued at the start, in the order it is needed — vmcnt retires loads in issue
-// order, so a wait for the first ones never waits for the later: the draw counter, then the slab
-// partials, then the dense bias, then the whole head region (every output's weights and bias) as
-// coalesced 16-B loads, staged into LDS beside h — and the row's uniforms are hashed from the
-// counter while the slabs are in flight. (Round 4: each wave used to load its outputs' weight
-// columns straight from HBM, lane f reading W[f][o] at a stride of A or R floats: one wave
-// instruction touched 16-40 cache lines, ~5,600 line requests per block for NATURE's 15 outputs
-// against ~500 for the region; the GEMV phase of the NATURE heads took 1.9 us.)
-constexpr int kHeadQ = 8;  // region quads per thread held in registers from the kernel start
-__device__ uint64_t g_zero_u64 = 0;  // read in place of an absent draw counter / sequence base
-
-template <int FT, int SB, int NT, bool POL>
-__device__ __forceinline__ void heads_row(int b, const float *__restrict__ slabs, int S, int B,
-                                          const float *__restrict__ fc_b, int act, float alpha, const HeadParams &hp,
-                                          float temp, float *__restrict__ H, float *__restrict__ v,
-                                          float *__restrict__ pi, float *__restrict__ rep, const SampleArgs &smp,
-                                          float *Ws) {
-  __shared__ float hs[NT * FT];
-  __shared__ float zs[64];
-  const int F = hp.F, O = 1 + hp.A + hp.R;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int FMAX = NT * FT / 64;  // feature terms per lane of a column walk
-  constexpr int NW = NT / 64;
-  // every load below is unconditional (clamped addresses, zeros by select): a guarded load would
-  // end its basic block with a wait for it
-  // (1) the draw counter and the sequence base (the uniforms need them first)
-  const uint64_t cnt = *(smp.counters ? smp.counters + b : &g_zero_u64);
-  const uint32_t seq_base = *(smp.seq_base ? smp.seq_base : reinterpret_cast<const uint32_t *>(&g_zero_u64));
-  // (2) the slab partials of the thread's features (S = 9 for the NIPS trunk: one batch)
-  const size_t zs_stride = (size_t)B * F;
-  float t[FT][SB];
-#pragma unroll
-  for (int fi = 0; fi < FT; ++fi) {
-    const float *p = slabs + (size_t)b * F + min((int)threadIdx.x + NT * fi, F - 1);
-#pragma unroll
-    for (int u = 0; u < SB; ++u) t[fi][u] = p[(size_t)min(u, S - 1) * zs_stride];
-  }
-  // (3) dense bias, then the head region's first KQ * NT quads (F > 256 on 512 threads: 6, so the
-  // whole region of an A = 18, R = 1 head set (Seaquest, 2,593 quads) is requested here — the
-  // remainder loop below was a second global round trip, ~0.5 us)
-  constexpr int KQ = NT == 512 ? 6 : kHeadQ;
-  float fb[FT];
-#pragma unroll
-  for (int fi = 0; fi < FT; ++fi) fb[fi] = fc_b[min((int)threadIdx.x + NT * fi, F - 1)];
-  const f32x4 *hsrc = reinterpret_cast<const f32x4 *>(hp.Wc);
-  f32x4 wq[KQ];
-#pragma unroll
-  for (int q = 0; q < KQ; ++q) wq[q] = hsrc[min((int)threadIdx.x + NT * q, hp.nq - 1)];
-  if (smp.advance && b == 0 && threadIdx.x == 0) {  // the replayed rollout's last reader has run
-    smp.advance[0] += smp.advance_by;
-    smp.advance[1] += smp.advance_by;
-  }
-  double ua = 0.0, ur = 0.0;
-  if (w == 0) row_uniforms(smp.seed, b + smp.row0, cnt, &ua, &ur);
-  // POL (e-greedy / argmax draw): the call's epsilon from the same counter, in the same shadow
-  double eps = 0.0;
-  if (POL && w == 0) eps = policy_epsilon(smp.policy, cnt);
-  // slab sum in slab order + bias + activation
-#pragma unroll
-  for (int fi = 0; fi < FT; ++fi) {
-    const int f = threadIdx.x + NT * fi;
-    float acc = 0.f;
-#pragma unroll
-    for (int u = 0; u < SB; ++u)
-      if (u < S) acc += t[fi][u];
-    for (int z = SB; z < S; ++z) acc += slabs[(size_t)b * F + min(f, F - 1) + (size_t)z * zs_stride];  // (S > SB)
-    const float h = act_fwd(acc + fb[fi], act, alpha);
-    if (f < F) {
-      hs[f] = h;
-      H[(size_t)b * F + f] = h;
-    }
-  }
-  // the head region into LDS (the rest of a region larger than KQ * NT quads loaded here)
-  f32x4 *wdst = reinterpret_cast<f32x4 *>(Ws);
-#pragma unroll
-  for (int q = 0; q < KQ; ++q)
-    if ((int)threadIdx.x + NT * q < hp.nq) wdst[threadIdx.x + NT * q] = wq[q];
-  for (int i = threadIdx.x + NT * KQ; i < hp.nq; i += NT) wdst[i] = hsrc[i];
-  __syncthreads();
-  MT_PROBE_AT(2, b, 1);
-  // logits: the same products and order as a column walk f = lane, lane + 64, ... then the bias.
-  // (The wave index through readfirstlane and, for F a multiple of 64, a wave-uniform term count:
-  // a per-lane guard made each term an exec-masked block with its own LDS round trip, and the
-  // column loop a divergent one — ~0.45 us per column of a wave, probe build.)
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  const int jn = F >> 6;
-  if ((F & 63) == 0) {
-    // The wave's features read once; outputs o and o + NW per pass, every operand of both columns
-    // (and their biases) requested at once. Lane offsets by 24-bit multiplies and wave-uniform term
-    // offsets (j clamped to the last real term): the per-term 32-bit multiplies were quarter-rate,
-    // and the bias a dependent LDS round trip after the reduction (round 6: 1.8 us for Seaquest's
-    // 20 outputs, probe build).
-    float hv[FMAX];
-#pragma unroll
-    for (int j = 0; j < FMAX; ++j) hv[j] = hs[min(lane + 64 * j, NT * FT - 1)];
-    for (int o0 = wu; o0 < O; o0 += 2 * NW) {
-      const int o1 = o0 + NW < O ? o0 + NW : o0;
-      int b0, s0, c0, b1, s1, c1;
-      head_col_lds(hp, o0, b0, s0, c0);
-      head_col_lds(hp, o1, b1, s1, c1);
-      const int l0 = b0 + __mul24(lane, s0), l1 = b1 + __mul24(lane, s1);
-      float w0[FMAX], w1[FMAX];
-#pragma unroll
-      for (int j = 0; j < FMAX; ++j) {
-        const int jj = min(j, jn - 1);
-        w0[j] = Ws[l0 + jj * 64 * s0];
-        w1[j] = Ws[l1 + jj * 64 * s1];
-      }
-      const float bias0 = Ws[c0], bias1 = Ws[c1];
-      float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-      for (int j = 0; j < FMAX; ++j)
-        if (j < jn) {
-          a0 += hv[j] * w0[j];
-          a1 += hv[j] * w1[j];
-        }
-      a0 = wave_sum(a0);
-      a1 = wave_sum(a1);
-      if (lane == 0) {
-        zs[o0] = a0 + bias0;
-        if (o1 != o0) zs[o1] = a1 + bias1;
-      }
-    }
-  } else {
-    for (int o = wu; o < O; o += NW) {
-      int base, stride, bias;
-      head_col_lds(hp, o, base, stride, bias);
-      float acc = 0.f;
-#pragma unroll
-      for (int j = 0; j < FMAX; ++j)
-        if (lane + 64 * j < F) acc += hs[lane + 64 * j] * Ws[base + (lane + 64 * j) * stride];
-      acc = wave_sum(acc);
-      if (lane == 0) zs[o] = acc + Ws[bias];
-    }
-  }
-  __syncthreads();
-  MT_PROBE_AT(2, b, 2);
-  if (w != 0) return;
-  const float z = lane < O ? zs[lane] : 0.f;
-  if (lane == 0) v[b] = z;
-  // actor logits sit in lanes 1..A, repetition logits in lanes 1+A..A+R: shift them to 0..
-  // (wave-uniform shortcuts with identical results for finite logits: x / 1 = x, and a one-way
-  // softmax is exp(0) / 1 = 1 — the two IEEE divisions and the whole repetition softmax were a
-  // third of this single wave's instructions for the non-FiGAR heads)
-  float za = __shfl(z, (lane + 1) & 63, 64);
-  float zr = __shfl(z, (lane + 1 + hp.A) & 63, 64);
-  if (temp != 1.f) {
-    za = za / temp;
-    zr = zr / temp;
-  }
-  const float pa = wave_softmax(za, lane, hp.A);
-  const float pr = hp.R == 1 ? (lane == 0 ? 1.f : 0.f) : wave_softmax(zr, lane, hp.R);
-  if (lane < hp.A) pi[(size_t)b * hp.A + lane] = pa;
-  if (lane < hp.R) rep[(size_t)b * hp.R + lane] = pr;
-  if (smp.counters) {
-    const int a = POL ? wave_choose(pa, hp.A, ua, eps) : wave_draw(pa, hp.A, ua);
-    const int r = POL ? wave_choose(pr, hp.R, ur, eps) : wave_draw(pr, hp.R, ur);
-    if (lane == 0) {
-      const uint32_t seq = seq_base + smp.seq;  // (graph replay: device base)
-      if (smp.packed) {  // tagged pair, one 8-byte store, no fence (SampleArgs::packed)
-        const uint64_t tag = (uint64_t)(seq & 0xffffu) << 16;
-        const uint64_t word = ((tag | (uint32_t)r) << 32) | tag | (uint32_t)a;
-        __hip_atomic_store(smp.packed + b, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else if (smp.pair) {
-        smp.pair[b] = a;
-        smp.pair[B + b] = r;
-      }
-      smp.counters[b] = cnt + 1;
-      smp.a_idx[b] = a;
-      smp.r_idx[b] = r;
-      if (smp.ready && !smp.packed) {  // release: the pair stores are visible to the host before the flag
-        __threadfence_system();
-        __hip_atomic_store(smp.ready + b, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
-}
-
-// POL: the draw's exploration policy is e-greedy or argmax (SampleArgs::policy). A template parameter,
-// not a run-time branch: the multinomial kernel (POL = false) is instruction for instruction the one
-// it was before the policy modes, on the single wave that ends every macro-step's chain.
-template <int FT, int SB, int NT, bool POL>
-__global__ __launch_bounds__(NT) void heads_fwd_kernel(const float *__restrict__ slabs, int S, int B,
-                                                        const float *__restrict__ fc_b, int act,
-                                                        float alpha, HeadParams hp, float temp,
-                                                        float *__restrict__ H, float *__restrict__ v,
-                                                        float *__restrict__ pi,
-                                                        float *__restrict__ rep, SampleArgs smp) {
-  extern __shared__ __attribute__((aligned(16))) float head_region[];
-  MT_PROBE_AT(2, blockIdx.x, 0);
-  heads_row<FT, SB, NT, POL>(blockIdx.x, slabs, S, B, fc_b, act, alpha, hp, temp, H, v, pi, rep, smp, head_region);
-  MT_PROBE_AT(2, blockIdx.x, 3);
-}
-
-// heads_fwd_kernel for F features (<= 512) and S slabs: one feature per thread (256 threads for
-// F <= 256, 512 above: the GEMV is instruction-issue bound with one wave per SIMD, so 8 waves take
-// fewer output passes each — round 6) and SB >= S slabs in registers (else one batch of 16).
-static int launch_heads(int rows, hipStream_t s, const float *slabs, int S, int B, const float *fc_b, int act,
-                        float alpha, const HeadParams &hp, float temp, float *H, float *v, float *pi, float *rep,
-                        const SampleArgs &smp) {
-  if (hp.F > 512 || 1 + hp.A + hp.R > kMaxHeads) {
-    set_error("heads: F = %d > 512 or %d outputs > %d", hp.F, 1 + hp.A + hp.R, kMaxHeads);
-    return MT_ERR_ARG;
-  }
-  // dynamic LDS: the head region (<= 64 outputs x 513 rows: 132 KB at most)
-  const size_t lds = (size_t)hp.nq * 16;
-  if (lds > kHeadRegionMaxBytes) {
-    set_error("heads: head region of %zu bytes exceeds the LDS", lds);
-    return MT_ERR_ARG;
-  }
-#define MT_HEADS_(FT_, SB_, NT_, POL_)                                                                       \
-  do {                                                                                                       \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set && lds > 64 * 1024) {                                                                      \
-      MT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&heads_fwd_kernel<FT_, SB_, NT_, POL_>),     \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));  \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL((heads_fwd_kernel<FT_, SB_, NT_, POL_>), dim3(rows), dim3(NT_), lds, s, slabs, S, B,    \
-                       fc_b, act, alpha, hp, temp, H, v, pi, rep, smp);                                      \
-  } while (0)
-#define MT_HEADS(FT_, SB_, NT_)                                                 \
-  do {                                                                          \
-    if (smp.counters && smp.policy.mode != MT_POLICY_MULTINOMIAL)               \
-      MT_HEADS_(FT_, SB_, NT_, true);                                           \
-    else                                                                        \
-      MT_HEADS_(FT_, SB_, NT_, false);                                          \
-  } while (0)
-  if (hp.F <= 256) {
-    if (S <= 1) MT_HEADS(1, 1, 256);
-    else if (S <= 9) MT_HEADS(1, 9, 256);
-    else MT_HEADS(1, 16, 256);
-  } else {
-    if (S <= 1) MT_HEADS(1, 1, 512);
-    else if (S <= 9) MT_HEADS(1, 9, 512);
-    else MT_HEADS(1, 16, 512);
-  }
-#undef MT_HEADS
-#undef MT_HEADS_
-  MT_LAUNCHED();
-  return MT_OK;
-}
-
-#ifdef MT_PROBE
-extern "C" int mt_probe_read(unsigned long long *out, size_t n) {
-  MT_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mt_probe_buf), std::min(n, sizeof(mt_probe_buf) / 8) * 8));
-  return MT_OK;
-}
-extern "C" int mt_probe_read_chain(unsigned long long *out, size_t n) {
-  MT_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mt_probe_chain), std::min(n, sizeof(mt_probe_chain) / 8) * 8));
-  return MT_OK;
-}
-extern "C" int mt_probe_read_chain_blocks(unsigned long long *out, size_t n) {
-  MT_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mt_probe_chainblk), std::min(n, sizeof(mt_probe_chainblk) / 8) * 8));
-  return MT_OK;
-}
-#endif
-
-
-// dL/dlogit for one softmax head (policy_v_network.py:29-57, :59-74), one wave, lanes [0, n):
-// objective = adv*log(p_sel + 1e-30) + beta*H,  H = -sum p*log(p + 1e-30),  L = -scale*objective.
-// Chain rule exactly as TF differentiates it: g_k = dL/dp_k, dz_k = p_k (g_k - sum_j p_j g_j),
-// dlogit_k = dz_k / temp. Returns lane's dlogit; *ent, *lsel receive H and log(p_sel+eps).
-__device__ __forceinline__ float head_softmax_grad(float p, int lane, int n, int sel, float adv,
-                                                   float beta, float scale, float temp, float *ent,
-                                                   float *lsel) {
-  const float eps = 1e-30f;
-  const bool on = lane < n;
-  const float pe = p + eps;
-  const float lp = on ? logf(pe) : 0.f;
-  const float e = wave_sum(on ? -(p * lp) : 0.f);
-  *ent = e;
-  *lsel = __shfl(lp, sel, 64);
-  // d objective / dp_k = adv*[k==sel]/(p+eps) + beta * d(-sum p log(p+eps))/dp_k
-  //                    = adv*[k==sel]/(p+eps) - beta*(log(p+eps) + p/(p+eps))
-  float dobj = on ? ((lane == sel ? adv / pe : 0.f) - beta * (lp + p / pe)) : 0.f;
-  const float g = -scale * dobj;
-  const float sg = wave_sum(on ? p * g : 0.f);
-  return on ? p * (g - sg) / temp : 0.f;
-}
-
-// One workgroup per row b: head gradients dz[b][0..O) and dH[b][f] = act'(H) * sum_o dz_o W[f][o].
-// Optional n-step scan inside the loss kernel (mt_returns_loss_backward): row b = t*E + e.
-struct ReturnsSrc {
-  const float *r = nullptr, *mask = nullptr, *VT = nullptr;  // r / mask [T][E] (host-mapped ok)
-  double gamma = 0.0;
-  int T = 0, E = 0;
-  float *y_out = nullptr, *adv_out = nullptr;
-  // bootstrap from the rollout's last chain without its heads kernel (mt_returns_loss_backward_boot):
-  // V(s_T)[e] = [act(sum_z boot_slabs[z][e] + fc_b), 1] . [Wc, bc] computed by the loss block
-  // itself (VT unused), written to vt_out[e] by the blocks of step 0
-  const float *boot_slabs = nullptr, *fc_b = nullptr;
-  int boot_S = 0;
-  float *vt_out = nullptr;
-  // BAYESIAN (mt_dropout_returns_loss_backward, the kernel's RV variant): the rollout's values [T][E].
-  // adv = R - v_roll[b], while the critic term and loss_terms keep the kernel's `v` (the redrawn v')
-  const float *v_roll = nullptr;
-};
-
-// V(s_T)[e] of the bootstrap (ReturnsSrc::boot_slabs): the dense layer's split-K slabs summed in
-// slab order + bias + act (heads_row's phase 1), then the critic's dot product as heads_row forms
-// it (lanes over features in 64-strides, DPP wave sum, + bias) from the head region in LDS (Ws).
-// Called by the whole block; the result is in *vt (LDS) after the call. stage(): the caller's LDS
-// stores of the head region, run after this block's slab loads are issued and before the barrier.
-template <class Pre, class Stage>
-__device__ __forceinline__ void boot_value(const ReturnsSrc &rs, const HeadParams &hp, int e, int act, float alpha,
-                                           const float *Ws, float *hsb, float *vt, const Pre &pre, const Stage &stage) {
-  const int F = hp.F;
-  const size_t zs_stride = (size_t)rs.E * F;
-  if (F <= 512 && rs.boot_S <= 16) {
-    // every slab partial and dense bias of the thread's features requested first, THEN pre() (the
-    // caller's pinned-memory reward loads): vector loads retire in issue order, so a PCIe load
-    // issued ahead of these made the slab sum wait for it (round 5)
-    float t[2][16], fb[2];
-#pragma unroll
-    for (int fi = 0; fi < 2; ++fi) {
-      const int fc = min((int)threadIdx.x + 256 * fi, F - 1);
-      const float *p = rs.boot_slabs + (size_t)e * F + fc;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) t[fi][u] = p[(size_t)min(u, rs.boot_S - 1) * zs_stride];
-      fb[fi] = rs.fc_b[fc];
-    }
-    pre();
-#pragma unroll
-    for (int fi = 0; fi < 2; ++fi) {
-      const int f = threadIdx.x + 256 * fi;
-      if (f < F) {
-        float acc = 0.f;
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-          if (u < rs.boot_S) acc += t[fi][u];
-        hsb[f] = act_fwd(acc + fb[fi], act, alpha);
-      }
-    }
-  } else {
-    pre();
-    for (int f = threadIdx.x; f < F; f += 256) {
-      const float *p = rs.boot_slabs + (size_t)e * F + f;
-      float acc = 0.f;
-      for (int z = 0; z < rs.boot_S; z += 16) {
-        float t[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) t[u] = p[(size_t)min(z + u, rs.boot_S - 1) * zs_stride];
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-          if (z + u < rs.boot_S) acc += t[u];
-      }
-      hsb[f] = act_fwd(acc + rs.fc_b[f], act, alpha);
-    }
-  }
-  stage();
-  __syncthreads();
-  if (threadIdx.x < 64) {  // heads_row's critic column: same products, same order
-    const int lane = threadIdx.x;
-    float acc = 0.f;
-    if ((F & 63) == 0) {
-      const int jn = F >> 6;
-      float hv[8], wv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        hv[j] = hsb[min(lane + 64 * j, 511)];
-        wv[j] = Ws[min(lane + 64 * j, F - 1)];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < jn) acc += hv[j] * wv[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (lane + 64 * j < F) acc += hsb[lane + 64 * j] * Ws[lane + 64 * j];
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) *vt = acc + Ws[F];
-  }
-  __syncthreads();
-}
-
-// returns_kernel's arithmetic for row b = (t, e): R from T-1 down to t, bit-identical to
-// mt_returns. Thread k < 256 brings step t + k's reward / mask in (rk, mk: requested by the caller
-// before its other work, one round trip), the rest load here; thread 0 scans (vb = V[b], which it
-// loaded with the head inputs). Called by the whole block.
-__device__ __forceinline__ void row_return(const ReturnsSrc &rs, float vb, int b, float vt,
-                                           float rk, float mk, float *ya, float *buf) {
-#pragma clang fp contract(off)
-  const int T = rs.T, E = rs.E;
-  const int t = b / E, e = b - t * E, n = T - t;  // steps t .. T-1
-  if ((int)threadIdx.x < n) {
-    buf[2 * threadIdx.x] = rk;
-    buf[2 * threadIdx.x + 1] = mk;
-  }
-  for (int k = threadIdx.x + 256; k < n; k += 256) {
-    buf[2 * k] = rs.r[(size_t)(t + k) * E + e];
-    buf[2 * k + 1] = rs.mask[(size_t)(t + k) * E + e];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float g32 = __fmul_rn((float)rs.gamma, vt);
-    double R = (double)buf[2 * (n - 1)] + (double)g32 * (double)buf[2 * (n - 1) + 1];
-    const double gd = rs.gamma;
-    for (int k = n - 2; k >= 0; --k) R = (double)buf[2 * k] + (gd * R) * (double)buf[2 * k + 1];
-    ya[0] = (float)R;
-    ya[1] = (float)(R - (double)vb);
-    rs.y_out[b] = ya[0];
-    rs.adv_out[b] = ya[1];
-  }
-  __syncthreads();
-}
-
-// RV (compile-time, BAYESIAN's fused update): the advantage's value is rs.v_roll[b], loaded with the
-// row's other head inputs ahead of the scan; RV = false is the kernel of every other arch, unchanged.
-template <bool RV>
-__global__ __launch_bounds__(256) void loss_bwd_kernel(
-    HeadParams hp, const float *__restrict__ H, const float *__restrict__ pi,
-    const float *__restrict__ rep, const float *__restrict__ v, const int32_t *__restrict__ a_idx,
-    const int32_t *__restrict__ r_idx, const float *__restrict__ y, const float *__restrict__ adv,
-    float beta, float scale, float temp, int act, float alpha, float *__restrict__ dz,
-    float *__restrict__ dH, float *__restrict__ loss_terms, ReturnsSrc rs) {
-  __shared__ float dzs[kMaxHeads];
-  __shared__ float ya[2];
-  __shared__ float buf[2 * kMaxScan];
-  extern __shared__ __attribute__((aligned(16))) float Ws[];  // the head region (HeadParams::nq quads)
-  const int b = blockIdx.x;
-  MT_PROBE_AT(4, b, 0);
-  const int A = hp.A, R = hp.R, O = 1 + A + R, F = hp.F;
-  // Every load that does not depend on the return is issued first, so its latency overlaps the
-  // scan's (the rewards / masks are read over PCIe from pinned memory): the row's head inputs
-  // (threads < 64), H[b][f] of the thread's features and the head region as coalesced 16-B loads
-  // (staged into LDS for the critic's dot product and dH; round 4: per-thread loads of W[f][.] at a
-  // stride of A or R floats made ~2,800 cache-line requests per block for NATURE's heads, queued
-  // ahead of the bootstrap slab loads).
-  const int lane = threadIdx.x;
-  float pa = 0.f, pr = 0.f, vb = 0.f, adv_in = 0.f, y_in = 0.f;
-  [[maybe_unused]] float vroll = 0.f;
-  int ai = 0, ri = 0;
-  if (threadIdx.x < 64) {
-    pa = lane < A ? pi[(size_t)b * A + lane] : 0.f;
-    pr = lane < R ? rep[(size_t)b * R + lane] : 0.f;
-    vb = v[b];
-    if constexpr (RV) vroll = rs.v_roll[b];
-    ai = a_idx[b];
-    ri = r_idx[b];
-    if (!rs.r) {
-      adv_in = adv[b];
-      y_in = y[b];
-    }
-  }
-  constexpr int FT = 2;  // F <= 512 in registers (more: read at the end)
-  float hv[FT];
-#pragma unroll
-  for (int fi = 0; fi < FT; ++fi) hv[fi] = H[(size_t)b * F + min((int)threadIdx.x + 256 * fi, F - 1)];
-  const f32x4 *hsrc = reinterpret_cast<const f32x4 *>(hp.Wc);
-  f32x4 wq[kHeadQ];
-#pragma unroll
-  for (int q = 0; q < kHeadQ; ++q) wq[q] = hsrc[min((int)threadIdx.x + 256 * q, hp.nq - 1)];
-  auto stage = [&]() {
-    f32x4 *wdst = reinterpret_cast<f32x4 *>(Ws);
-#pragma unroll
-    for (int q = 0; q < kHeadQ; ++q)
-      if ((int)threadIdx.x + 256 * q < hp.nq) wdst[threadIdx.x + 256 * q] = wq[q];
-    for (int i = threadIdx.x + 256 * kHeadQ; i < hp.nq; i += 256) wdst[i] = hsrc[i];
-  };
-  bool staged = false;
-  if (rs.r) {
-    // this row's rewards / masks (pinned host memory, a PCIe round trip): requested right behind the
-    // bootstrap slab loads (boot_value's pre), whose sum would otherwise wait for them
-    float rk = 0.f, mk = 0.f;
-    auto rewards = [&]() {
-      const int t = b / rs.E, e = b - t * rs.E;
-      if ((int)threadIdx.x < rs.T - t) {
-        rk = rs.r[(size_t)(t + threadIdx.x) * rs.E + e];
-        mk = rs.mask[(size_t)(t + threadIdx.x) * rs.E + e];
-      }
-    };
-    float vt;
-    if (rs.boot_slabs) {
-      __shared__ float hsb[512];
-      __shared__ float vts;
-      const int e = b % rs.E;
-      boot_value(rs, hp, e, act, alpha, Ws, hsb, &vts, rewards, stage);
-      staged = true;
-      vt = vts;
-      if (rs.vt_out && b < rs.E && threadIdx.x == 0) rs.vt_out[e] = vt;
-    } else {
-      rewards();
-      vt = rs.VT[b % rs.E];
-    }
-    MT_PROBE_AT(4, b, 1);
-    row_return(rs, RV ? vroll : vb, b, vt, rk, mk, ya, buf);
-  }
-  MT_PROBE_AT(4, b, 2);
-  if (!staged) stage();  // (visible to every thread after the barrier below)
-  if (threadIdx.x < 64) {
-    const float ad = rs.r ? ya[1] : adv_in;
-    const float yb = rs.r ? ya[0] : y_in;
-    float ent_a, ls_a, ent_r, ls_r;
-    const float ga = head_softmax_grad(pa, lane, A, ai, ad, beta, scale, temp, &ent_a, &ls_a);
-    const float gr = head_softmax_grad(pr, lane, R, ri, ad, beta, scale, temp, &ent_r, &ls_r);
-    const float diff = yb - vb;
-    // d/dv of scale * 0.25 * (y - v)^2  (policy_v_network.py:25-26)
-    const float gv = scale * 0.25f * 2.0f * (vb - yb);
-    if (lane == 0) dzs[0] = gv;
-    if (lane < A) dzs[1 + lane] = ga;
-    if (lane < R) dzs[1 + A + lane] = gr;
-    if (lane == 0 && loss_terms) {
-      loss_terms[(size_t)b * 4 + 0] = 0.25f * diff * diff;
-      loss_terms[(size_t)b * 4 + 1] = -((ls_a + ls_r) * ad);
-      loss_terms[(size_t)b * 4 + 2] = ent_a;
-      loss_terms[(size_t)b * 4 + 3] = ent_r;
-    }
-  }
-  __syncthreads();
-  MT_PROBE_AT(4, b, 3);
-  for (int o = threadIdx.x; o < O; o += 256) dz[(size_t)b * O + o] = dzs[o];
-  // dH[b][f] = act'(H) * (dz_c Wc[f] + actor terms + repetition terms), in that order
-  const int oa = (int)(hp.Wa - hp.Wc), orr = (int)(hp.Wr - hp.Wc);
-  auto dh = [&](int f, float h) {
-    float acc = dzs[0] * Ws[f];
-    for (int k = 0; k < A; ++k) acc += dzs[1 + k] * Ws[oa + f * A + k];
-    for (int k = 0; k < R; ++k) acc += dzs[1 + A + k] * Ws[orr + f * R + k];
-    dH[(size_t)b * F + f] = acc * act_bwd(h, act, alpha);
-  };
-#pragma unroll
-  for (int fi = 0; fi < FT; ++fi)
-    if ((int)threadIdx.x + 256 * fi < F) dh(threadIdx.x + 256 * fi, hv[fi]);
-  for (int f = threadIdx.x + 256 * FT; f < F; f += 256) dh(f, H[(size_t)b * F + f]);  // (F > 512: not built today)
-  MT_PROBE_AT(4, b, 4);
-}
-
-// Head weight/bias gradient: G[f][o] = sum_b [H,1][b][f] * dz[b][o], scattered into the three
-// (w, b) variable pairs of the flat gradient. Block = (64 features, output o): column o of dz is
-// staged in LDS, the 4 waves take contiguous quarters of the rows (H read coalesced: consecutive
-// lanes = consecutive features, 4 independent accumulators per lane), and the 4 wave partials are
-// added in wave order through LDS (deterministic).
-__device__ __forceinline__ void head_wgrad_body(const float *__restrict__ H, const float *__restrict__ dz, int B,
-                                                int F, int A, int R, float *__restrict__ gc, float *__restrict__ ga,
-                                                float *__restrict__ gr, int bx, int o, float *dzs) {
-  // dzs: [B] column o, then [4][64] partials
-  const int O = 1 + A + R;
-  for (int i = threadIdx.x; i < B; i += 256) dzs[i] = dz[(size_t)i * O + o];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int f = bx * 64 + lane;  // f == F is the bias row
-  const int q = (B + 3) / 4, b0 = w * q, b1 = min(B, b0 + q);
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  if (f <= F) {
-    int b = b0;
-    if (f < F) {
-      // 16 rows' loads in flight per trip (a 4-row trip waited out one load latency per 4 rows);
-      // accumulator u still takes rows b0 + u, b0 + 4 + u, ... in order
-      for (; b + 15 < b1; b += 16) {
-        float h[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) h[u] = H[(size_t)(b + u) * F + f];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) a[u & 3] += h[u] * dzs[b + u];
-      }
-      for (; b + 3 < b1; b += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] += H[(size_t)(b + u) * F + f] * dzs[b + u];
-      }
-      for (; b < b1; ++b) a[0] += H[(size_t)b * F + f] * dzs[b];
-    } else {
-      for (; b < b1; ++b) a[0] += dzs[b];
-    }
-  }
-  float *part = dzs + B;
-  part[w * 64 + lane] = (a[0] + a[1]) + (a[2] + a[3]);
-  __syncthreads();
-  if (w != 0 || f > F) return;
-  const float acc = ((part[lane] + part[64 + lane]) + part[128 + lane]) + part[192 + lane];
-  if (o == 0)
-    gc[f] = acc;  // [F][1] weights then the bias at index F
-  else if (o <= A)
-    ga[(size_t)f * A + (o - 1)] = acc;
-  else
-    gr[(size_t)f * R + (o - 1 - A)] = acc;
-}
-
-// The head weight gradient as a job of a grouped launch: block (f chunk of 64, output o).
-struct HeadWgradJob {
-  const float *H, *dz;
-  int B, F, A, R;
-  float *gc, *ga, *gr;
-  __host__ __device__ int gx() const { return (F + 1 + 63) / 64; }
-  __host__ __device__ int blocks() const { return gx() * (1 + A + R); }
-  size_t lds() const { return sizeof(float) * ((size_t)B + 4 * 64); }
-  __device__ __forceinline__ void run(int id, float *smem) const {
-    head_wgrad_body(H, dz, B, F, A, R, gc, ga, gr, id % gx(), id / gx(), smem);
-  }
-};
 
 // ---------------------------------------------------------------------------------------------
 // Layer drivers
@@ -1279,6 +199,8 @@ static int trunk_forward(const mt_net *n, const float *P, const void *x, int B, 
 struct NormOut {
   float *partials = nullptr;  // [MT_NORM_PARTIALS]
   size_t n = 0;               // gradient floats
+  NormOut() = default;
+  NormOut(float *partials_, const mt_net *net) : partials(partials_), n(net->nparams) {}
 };
 
 template <class Ar, int I, class X = NoJob>
@@ -1449,9 +371,7 @@ static int forward_impl(const mt_net *n, const float *P, const uint8_t *obs, int
   const WsLayout L = ws_layout<Ar>(n, B);
   const ActRows A = act_rows<Ar>(n, ws, L, tr);
   if (marks) MT_HIP(hipEventRecord(marks[0], s));
-  FwdExtras ex;
-  ex.st = st;
-  ex.sync = reinterpret_cast<uint32_t *>(ws + L.sync);
+  const FwdExtras ex{st, reinterpret_cast<uint32_t *>(ws + L.sync)};
   MT_TRY((trunk_forward<Ar>(n, P, obs, B, A.base, A.L, s, ex)));
   const float *flat = layer_out<Ar, Ar::NCONV - 1>(A.base, A.L);
   // dense layer (networks.py:57-70), split-K partial slabs; heads kernel finishes bias + act.
@@ -1507,24 +427,36 @@ static int forward_boot_impl(const mt_net *n, const float *P, const uint8_t *obs
       set_error("sequence-base advance: row-split dense layers only");
       return MT_ERR_UNSUPPORTED;
     }
-    FwdExtras ex;
-    ex.st = st;
-    ex.sync = reinterpret_cast<uint32_t *>(ws + L.sync);
+    const FwdExtras ex{st, reinterpret_cast<uint32_t *>(ws + L.sync)};
     MT_TRY((trunk_forward<Ar>(n, P, obs, B, ws, L, s, ex)));
     return launch_fc<Ar>(layer_out<Ar, Ar::NCONV - 1>(ws, L), B, Wfc, ws + L.fcslab, L.fc_splits, s, advance,
                          advance_by);
   }
 }
 
+// The loss arguments of a backward, host side (the kernel takes them as separate pointers): the policy
+// outputs and value of the rows, the indices drawn, the returns and advantages, and where the gradient
+// and the optional per-row loss terms [B][4] go.
+struct LossArgs {
+  const float *pi, *rep, *v;
+  const int32_t *a_idx, *r_idx;
+  const float *y, *adv;
+  float beta;
+  float *grad, *loss_terms;
+};
+
 // Loss + head gradients (policy_v_network.py:25-74): writes dz, dH (masked by the trunk output's
-// activation derivative) and the three head (w, b) gradients. Every variable's gradient is
-// overwritten by the backward (no accumulation), so grad is not cleared: its alignment padding
-// must be zero once (include/manette_hip.h, mt_loss_backward).
+// activation derivative); the head weight gradient (head_wgrad_job) that every caller groups into a
+// later launch writes the three head (w, b) gradients, and its LDS stage bounds the batch here, before
+// anything is enqueued. Every variable's gradient is overwritten by the backward (no accumulation), so
+// grad is not cleared: its alignment padding must be zero once (include/manette_hip.h, mt_loss_backward).
 template <class Ar>
-static int loss_bwd_launch(const mt_net *n, const float *P, int B, float *ws, const WsLayout &L, const float *pi,
-                           const float *rep, const float *v, const int32_t *a_idx, const int32_t *r_idx,
-                           const float *y, const float *adv, float beta, float *loss_terms, hipStream_t s,
-                           const ReturnsSrc &rs = ReturnsSrc{}) {
+static int loss_bwd_launch(const mt_net *n, const float *P, int B, float *ws, const WsLayout &L, const LossArgs &la,
+                           hipStream_t s, const ReturnsSrc &rs = ReturnsSrc{}) {
+  if (sizeof(float) * ((size_t)B + 4 * 64) > 160 * 1024) {  // HeadWgradJob::lds()
+    set_error("batch %d exceeds the head-gradient LDS stage", B);
+    return MT_ERR_ARG;
+  }
   // loss scaling 5.0 and the batch mean (policy_v_network.py:70-74): scale = 5/B.
   const float scale = 5.0f / (float)B;
   HeadParams hp = head_params(n, P);
@@ -1542,16 +474,11 @@ static int loss_bwd_launch(const mt_net *n, const float *P, int B, float *ws, co
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadRegionMaxBytes));
     attr_set = true;
   }
-  if (rs.v_roll) {  // (only with the scan: mt_dropout_returns_loss_backward)
-    MT_CHECK_ARG(rs.r && !rs.boot_slabs, "rollout values need the in-kernel scan with a finished v_boot");
-    hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(B), dim3(256), lds, s, hp, ws + L.H, pi, rep, v, a_idx, r_idx, y,
-                       adv, beta, scale, n->cfg.softmax_temp, n->cfg.activation, n->cfg.alpha_leaky, ws + L.dz,
-                       ws + L.dH, loss_terms, rs);
-  } else {
-    hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(B), dim3(256), lds, s, hp, ws + L.H, pi, rep, v, a_idx, r_idx, y,
-                       adv, beta, scale, n->cfg.softmax_temp, n->cfg.activation, n->cfg.alpha_leaky, ws + L.dz,
-                       ws + L.dH, loss_terms, rs);
-  }
+  // (rollout values only with the scan: mt_dropout_returns_loss_backward)
+  MT_CHECK_ARG(!rs.v_roll || (rs.r && !rs.boot_slabs), "rollout values need the in-kernel scan with a finished v_boot");
+  hipLaunchKernelGGL(rs.v_roll ? loss_bwd_kernel<true> : loss_bwd_kernel<false>, dim3(B), dim3(256), lds, s, hp,
+                     ws + L.H, la.pi, la.rep, la.v, la.a_idx, la.r_idx, la.y, la.adv, la.beta, scale, n->cfg.softmax_temp,
+                     n->cfg.activation, n->cfg.alpha_leaky, ws + L.dz, ws + L.dH, la.loss_terms, rs);
   MT_LAUNCHED();
   return MT_OK;
 }
@@ -1560,19 +487,6 @@ template <class Ar>
 static HeadWgradJob head_wgrad_job(const mt_net *n, int B, float *ws, const WsLayout &L, float *grad) {
   return HeadWgradJob{ws + L.H, ws + L.dz, B, Ar::F, n->cfg.num_actions, n->cfg.num_reps,
                       grad + n->off_critic, grad + n->off_actor, grad + n->off_rep};
-}
-
-template <class Ar>
-static int heads_backward(const mt_net *n, const float *P, int B, float *ws, const WsLayout &L, const float *pi,
-                          const float *rep, const float *v, const int32_t *a_idx, const int32_t *r_idx,
-                          const float *y, const float *adv, float beta, float *grad, float *loss_terms,
-                          hipStream_t s) {
-  if (sizeof(float) * ((size_t)B + 4 * 64) > 160 * 1024) {
-    set_error("batch %d exceeds the head-gradient LDS stage", B);
-    return MT_ERR_ARG;
-  }
-  MT_TRY(loss_bwd_launch<Ar>(n, P, B, ws, L, pi, rep, v, a_idx, r_idx, y, adv, beta, loss_terms, s));
-  return launch_group(s, head_wgrad_job<Ar>(n, B, ws, L, grad));
 }
 
 // Launches of backward_impl up to the one that completes every dense / head gradient: the loss
@@ -1585,19 +499,13 @@ constexpr int kDenseBucketLaunches = 2;
 // per conv layer I (top down): conv dX + conv dW + the slab sum of layer I+1's dW | conv1's slab
 // sum — 2 + NCONV launches (the max pools are fused into the conv products) instead of two or three per layer.
 template <class Ar>
-static int backward_impl(const mt_net *n, const float *P, const uint8_t *obs, int B, float *ws,
-                         const float *pi, const float *rep, const float *v, const int32_t *a_idx,
-                         const int32_t *r_idx, const float *y, const float *adv, float beta,
-                         float *grad, float *loss_terms, hipStream_t s, const ReturnsSrc &rs = ReturnsSrc{},
-                         const NormOut &no = NormOut{}) {
+static int backward_impl(const mt_net *n, const float *P, const uint8_t *obs, int B, float *ws, const LossArgs &la,
+                         hipStream_t s, const ReturnsSrc &rs = ReturnsSrc{}, const NormOut &no = NormOut{}) {
   const WsLayout L = ws_layout<Ar>(n, B);
   const int act = n->cfg.activation;
   const float al = n->cfg.alpha_leaky;
-  if (sizeof(float) * ((size_t)B + 4 * 64) > 160 * 1024) {
-    set_error("batch %d exceeds the head-gradient LDS stage", B);
-    return MT_ERR_ARG;
-  }
-  MT_TRY(loss_bwd_launch<Ar>(n, P, B, ws, L, pi, rep, v, a_idx, r_idx, y, adv, beta, loss_terms, s, rs));
+  float *grad = la.grad;
+  MT_TRY(loss_bwd_launch<Ar>(n, P, B, ws, L, la, s, rs));
   constexpr int K = Ar::NCONV - 1;
   const float *flat = layer_out<Ar, K>(ws, L);
   const float *Wfc = P + n->off_fc;
@@ -1667,21 +575,53 @@ static int dropout_redraw_impl(const mt_net *net, const float *params, int batch
 // ---------------------------------------------------------------------------------------------
 using namespace mt;
 
-#define MT_ARCH_SWITCH(net, ...)                                                   \
-  do {                                                                              \
-    const int arch_ = (net)->cfg.arch, d_ = (net)->cfg.depth;                       \
-    if (arch_ == MT_ARCH_NIPS && d_ == 1) { using Ar = NipsArch<4>; __VA_ARGS__; }         \
-    else if (arch_ == MT_ARCH_NIPS && d_ == 3) { using Ar = NipsArch<12>; __VA_ARGS__; }   \
-    else if (arch_ == MT_ARCH_NATURE && d_ == 1) { using Ar = NatureArch<4>; __VA_ARGS__; } \
-    else if (arch_ == MT_ARCH_NATURE && d_ == 3) { using Ar = NatureArch<12>; __VA_ARGS__; } \
-    else if (arch_ == MT_ARCH_PWYX && d_ == 1) { using Ar = PwyxArch<4>; __VA_ARGS__; }     \
-    else if (arch_ == MT_ARCH_PWYX && d_ == 3) { using Ar = PwyxArch<12>; __VA_ARGS__; }    \
-    else if (arch_ == MT_ARCH_LSTM && d_ == 1) { using Ar = LstmArch<4>; __VA_ARGS__; }     \
-    else if (arch_ == MT_ARCH_LSTM && d_ == 3) { using Ar = LstmArch<12>; __VA_ARGS__; }    \
-    else if (arch_ == MT_ARCH_BAYESIAN && d_ == 1) { using Ar = BayesArch<4>; __VA_ARGS__; } \
-    else if (arch_ == MT_ARCH_BAYESIAN && d_ == 3) { using Ar = BayesArch<12>; __VA_ARGS__; } \
-    else { set_error("arch %d depth %d not built", arch_, d_); return MT_ERR_UNSUPPORTED; } \
-  } while (0)
+// The architectures built into the library — the only list of them. fn is a generic lambda called with
+// the net's arch descriptor as a type tag (`using Ar = decltype(ar);`); its status is returned.
+template <class Fn>
+static int with_arch(const mt_net *net, const Fn &fn) {
+  const int arch = net->cfg.arch, d = net->cfg.depth;
+  if (arch == MT_ARCH_NIPS && d == 1) return fn(NipsArch<4>{});
+  if (arch == MT_ARCH_NIPS && d == 3) return fn(NipsArch<12>{});
+  if (arch == MT_ARCH_NATURE && d == 1) return fn(NatureArch<4>{});
+  if (arch == MT_ARCH_NATURE && d == 3) return fn(NatureArch<12>{});
+  if (arch == MT_ARCH_PWYX && d == 1) return fn(PwyxArch<4>{});
+  if (arch == MT_ARCH_PWYX && d == 3) return fn(PwyxArch<12>{});
+  if (arch == MT_ARCH_LSTM && d == 1) return fn(LstmArch<4>{});
+  if (arch == MT_ARCH_LSTM && d == 3) return fn(LstmArch<12>{});
+  if (arch == MT_ARCH_BAYESIAN && d == 1) return fn(BayesArch<4>{});
+  if (arch == MT_ARCH_BAYESIAN && d == 3) return fn(BayesArch<12>{});
+  set_error("arch %d depth %d not built", arch, d);
+  return MT_ERR_UNSUPPORTED;
+}
+
+// MT_OK, or the refusal of a workspace shorter than its layout.
+static int check_ws(size_t ws_bytes, const WsLayout &L) {
+  if (ws_bytes < L.total * sizeof(float)) {
+    set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
+    return MT_ERR_WORKSPACE;
+  }
+  return MT_OK;
+}
+// The same for the layout of `batch` rows, which *L receives.
+template <class Ar>
+static int checked_layout(const mt_net *net, int batch, size_t ws_bytes, WsLayout *L = nullptr) {
+  const WsLayout l = ws_layout<Ar>(net, batch);
+  if (L) *L = l;
+  return check_ws(ws_bytes, l);
+}
+// The same for a workspace and the bootstrap forward's (mt_returns_loss_backward_boot), refused together.
+template <class Ar>
+static int checked_layout_boot(const mt_net *net, int batch, size_t ws_bytes, WsLayout *L, int boot_batch,
+                               size_t boot_ws_bytes, WsLayout *LB) {
+  *L = ws_layout<Ar>(net, batch);
+  *LB = ws_layout<Ar>(net, boot_batch);
+  if (ws_bytes < L->total * sizeof(float) || boot_ws_bytes < LB->total * sizeof(float)) {
+    set_error("workspace %zu / bootstrap workspace %zu < %zu / %zu bytes", ws_bytes, boot_ws_bytes,
+              L->total * sizeof(float), LB->total * sizeof(float));
+    return MT_ERR_WORKSPACE;
+  }
+  return MT_OK;
+}
 
 extern "C" int mt_net_create(const mt_net_config *cfg, mt_net **out) {
   MT_CHECK_ARG(cfg && out, "null argument");
@@ -1697,27 +637,37 @@ extern "C" int mt_net_create(const mt_net_config *cfg, mt_net **out) {
   n->cfg = *cfg;
   n->C = 4 * cfg->depth;
   n->O = 1 + cfg->num_actions + cfg->num_reps;
-  const int arch = cfg->arch, d = cfg->depth;
-  if (arch == MT_ARCH_NIPS && d == 1) build_layout<NipsArch<4>>(n);
-  else if (arch == MT_ARCH_NIPS && d == 3) build_layout<NipsArch<12>>(n);
-  else if (arch == MT_ARCH_NATURE && d == 1) build_layout<NatureArch<4>>(n);
-  else if (arch == MT_ARCH_NATURE && d == 3) build_layout<NatureArch<12>>(n);
-  else if (arch == MT_ARCH_PWYX && d == 1) build_layout<PwyxArch<4>>(n);
-  else if (arch == MT_ARCH_PWYX && d == 3) build_layout<PwyxArch<12>>(n);
-  else if (arch == MT_ARCH_LSTM && d == 1) build_layout_lstm<LstmArch<4>>(n);
-  else if (arch == MT_ARCH_LSTM && d == 3) build_layout_lstm<LstmArch<12>>(n);
-  else if (arch == MT_ARCH_BAYESIAN && d == 1) build_layout<BayesArch<4>>(n);
-  else if (arch == MT_ARCH_BAYESIAN && d == 3) build_layout<BayesArch<12>>(n);
-  else {
+  const int rc = with_arch(n, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    if constexpr (Ar::LSTM) build_layout_lstm<Ar>(n);
+    else build_layout<Ar>(n);
+    return MT_OK;
+  });
+  if (rc != MT_OK) {  // (the depth is 1 or 3: no such arch)
     delete n;
-    set_error("arch %d not built into this library", arch);
-    return MT_ERR_UNSUPPORTED;
+    set_error("arch %d not built into this library", cfg->arch);
+    return rc;
   }
   *out = n;
   return MT_OK;
 }
 
 extern "C" void mt_net_destroy(mt_net *net) { delete net; }
+
+#ifdef MT_PROBE
+extern "C" int mt_probe_read(unsigned long long *out, size_t n) {
+  MT_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mt_probe_buf), std::min(n, sizeof(mt_probe_buf) / 8) * 8));
+  return MT_OK;
+}
+extern "C" int mt_probe_read_chain(unsigned long long *out, size_t n) {
+  MT_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mt_probe_chain), std::min(n, sizeof(mt_probe_chain) / 8) * 8));
+  return MT_OK;
+}
+extern "C" int mt_probe_read_chain_blocks(unsigned long long *out, size_t n) {
+  MT_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mt_probe_chainblk), std::min(n, sizeof(mt_probe_chainblk) / 8) * 8));
+  return MT_OK;
+}
+#endif
 
 extern "C" int mt_net_num_params(const mt_net *net, size_t *n) {
   MT_CHECK_ARG(net && n, "null argument");
@@ -1763,13 +713,17 @@ extern "C" int mt_net_feature_dim(const mt_net *net, int *f) {
 extern "C" int mt_net_workspace_bytes(const mt_net *net, int batch, size_t *bytes) {
   MT_CHECK_ARG(net && bytes, "null argument");
   MT_CHECK_ARG(batch >= 1, "batch must be >= 1");
-  MT_ARCH_SWITCH(net, { *bytes = ws_layout<Ar>(net, batch).total * sizeof(float); });
-  return MT_OK;
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    *bytes = ws_layout<Ar>(net, batch).total * sizeof(float);
+    return MT_OK;
+  });
 }
 
 extern "C" int mt_net_backward_bucket_launches(const mt_net *net, int *launches) {
   MT_CHECK_ARG(net && launches, "null argument");
-  MT_ARCH_SWITCH(net, {
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if constexpr (Ar::LSTM) {
       set_error("the LSTM backward is not bucketed");
       return MT_ERR_UNSUPPORTED;
@@ -1778,9 +732,9 @@ extern "C" int mt_net_backward_bucket_launches(const mt_net *net, int *launches)
       return MT_ERR_UNSUPPORTED;
     } else {
       *launches = kDenseBucketLaunches;  // backward_impl: loss | dense dX + dense dW + head dW | convs
+      return MT_OK;
     }
   });
-  return MT_OK;
 }
 
 // Byte range of a stored forward value in a workspace (diagnostics / parity; mt_net_workspace_region):
@@ -1838,25 +792,14 @@ static int ws_region(const WsLayout &L, int kind, int layer, size_t rows, size_t
   return MT_ERR_ARG;
 }
 
-template <class Ar>
-static int ws_region_windows(const mt_net *net, int a, int kind, int layer, size_t *offset, size_t *bytes) {
-  const WsLayout L = lstm_ws_layout<Ar>(net, a, nullptr);
-  return ws_region<Ar>(L, kind, layer, kind == 2 ? (size_t)a : (size_t)a * Ar::STEPS, offset, bytes);
-}
-
-template <class Ar>
-static int ws_region_frames(const mt_net *net, int E, int T, int kind, int layer, size_t *offset, size_t *bytes) {
-  const LstmFrameWs X = lstm_frame_layout<Ar>(net, E, T);
-  return ws_region<Ar>(X.L, kind, layer, kind == 2 ? (size_t)X.W : (size_t)X.R_max, offset, bytes);
-}
-
 extern "C" int mt_net_workspace_region(const mt_net *net, int layout, int a, int b, int kind, int layer,
                                        size_t *offset, size_t *bytes) {
   MT_CHECK_ARG(net && offset && bytes, "null argument");
   MT_CHECK_ARG(a >= 1 && (layout != 1 || b >= 1) && kind >= 0 && kind <= 7, "bad sizes or kind");
   MT_CHECK_ARG(kind < 4 || layout == 0,
                "the counter region (kind 4) and the dropout regions (5-7) are in the layout-0 workspace");
-  MT_ARCH_SWITCH(net, {
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if (layout == 0) {
       if constexpr (Ar::LSTM) {
         set_error("layout 0 is the non-LSTM workspace");
@@ -1868,15 +811,17 @@ extern "C" int mt_net_workspace_region(const mt_net *net, int layout, int a, int
       if constexpr (!Ar::LSTM) {
         set_error("layouts 1 and 2 are LSTM workspaces");
         return MT_ERR_ARG;
-      } else {
-        return layout == 1 ? ws_region_frames<Ar>(net, a, b, kind, layer, offset, bytes)
-                           : ws_region_windows<Ar>(net, a, kind, layer, offset, bytes);
+      } else if (layout == 1) {  // the frame store of E = a envs, T = b steps
+        const LstmFrameWs X = lstm_frame_layout<Ar>(net, a, b);
+        return ws_region<Ar>(X.L, kind, layer, kind == 2 ? (size_t)X.W : (size_t)X.R_max, offset, bytes);
+      } else {  // a windows of STEPS frames each
+        return ws_region<Ar>(lstm_ws_layout<Ar>(net, a, nullptr), kind, layer,
+                             kind == 2 ? (size_t)a : (size_t)a * Ar::STEPS, offset, bytes);
       }
     }
     set_error("layout %d", layout);
     return MT_ERR_ARG;
   });
-  return MT_OK;
 }
 
 extern "C" int mt_forward(const mt_net *net, const float *params, const uint8_t *obs, int batch,
@@ -1910,9 +855,7 @@ static int trunk_infer_impl(const mt_net *n, const float *P, const uint8_t *obs,
       MT_LAUNCHED();
       return MT_OK;
     } else {
-      FwdExtras ex;
-      ex.st = st;
-      ex.sync = reinterpret_cast<uint32_t *>(ws + L.sync);
+      const FwdExtras ex{st, reinterpret_cast<uint32_t *>(ws + L.sync)};
       MT_TRY((trunk_forward<Ar>(n, P, obs, B, ws, L, s, ex)));
       return launch_fc<Ar>(layer_out<Ar, Ar::NCONV - 1>(ws, L), B, Wfc, ws + L.fcslab, L.fc_splits, s);
     }
@@ -1923,15 +866,11 @@ extern "C" int mt_forward_trunk(const mt_net *net, const float *params, const ui
                                 size_t ws_bytes, mt_stream_t stream) {
   MT_CHECK_ARG(net && params && obs && ws, "null argument");
   MT_CHECK_ARG(batch >= 1, "batch must be >= 1");
-  MT_ARCH_SWITCH(net, {
-    const WsLayout L = ws_layout<Ar>(net, batch);
-    if (ws_bytes < L.total * sizeof(float)) {
-      set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-      return MT_ERR_WORKSPACE;
-    }
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(checked_layout<Ar>(net, batch, ws_bytes));
     return trunk_infer_impl<Ar>(net, params, obs, batch, (float *)ws, (hipStream_t)stream);
   });
-  return MT_OK;
 }
 
 extern "C" int mt_forward_trunk_stacking(const mt_net *net, const float *params, const uint8_t *prev,
@@ -1944,12 +883,9 @@ extern "C" int mt_forward_trunk_stacking(const mt_net *net, const float *params,
   st.ready = ready;
   st.tag = tag & 0x1fffffffu;
   st.status = status;
-  MT_ARCH_SWITCH(net, {
-    const WsLayout L = ws_layout<Ar>(net, batch);
-    if (ws_bytes < L.total * sizeof(float)) {
-      set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-      return MT_ERR_WORKSPACE;
-    }
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(checked_layout<Ar>(net, batch, ws_bytes));
     if constexpr (Ar::LSTM) {
       set_error("stacking trunk: the NIPS, gray NATURE and PWYX archs (the LSTM steps: mt_lstm_step_forward)");
       return MT_ERR_UNSUPPORTED;
@@ -1960,7 +896,6 @@ extern "C" int mt_forward_trunk_stacking(const mt_net *net, const float *params,
       return trunk_infer_impl<Ar>(net, params, out, batch, (float *)ws, (hipStream_t)stream, &st);
     }
   });
-  return MT_OK;
 }
 
 extern "C" int mt_forward_rows(const mt_net *net, const float *params, const uint8_t *obs, int batch, void *ws,
@@ -1987,12 +922,9 @@ int mt::forward_sample(const mt_net *net, const float *params, const uint8_t *ob
   // (smp without counters: no draw — the replayed rollout graph's bootstrap carries only `advance`)
   MT_CHECK_ARG(!smp || !smp->counters || (smp->a_idx && smp->r_idx), "null sample buffer");
   MT_CHECK_ARG(batch >= 1, "batch must be >= 1");
-  MT_ARCH_SWITCH(net, {
-    const WsLayout L = ws_layout<Ar>(net, batch);
-    if (ws_bytes < L.total * sizeof(float)) {
-      set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-      return MT_ERR_WORKSPACE;
-    }
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(checked_layout<Ar>(net, batch, ws_bytes));
     if (tr) {
       MT_CHECK_ARG(!Ar::LSTM, "train-row forwards are not built for the LSTM arch (frame store: mt_lstm_*)");
       MT_CHECK_ARG(tr->ws && tr->rows >= 1 && tr->row0 >= 0 && tr->row0 + batch <= tr->rows,
@@ -2003,34 +935,30 @@ int mt::forward_sample(const mt_net *net, const float *params, const uint8_t *ob
         return MT_ERR_WORKSPACE;
       }
     }
-    if constexpr (Ar::LSTM)
+    if constexpr (Ar::LSTM) {
       return lstm_forward_impl<Ar>(net, params, obs, batch, (float *)ws, v, pi, rep, smp, stream);
-    else
+    } else {
       MT_CHECK_ARG(!st || infer, "stacking forward is an inference forward");
       return infer ? forward_infer_impl<Ar>(net, params, obs, batch, (float *)ws, v, pi, rep, smp, stream, tr, st,
                                             marks)
                    : forward_impl<Ar>(net, params, obs, batch, (float *)ws, v, pi, rep, smp, stream, tr, marks);
+    }
   });
-  return MT_OK;
 }
 
 int mt::forward_boot(const mt_net *net, const float *params, const uint8_t *obs, int batch, void *ws,
                      size_t ws_bytes, hipStream_t stream, const StackSrc *st, uint32_t *advance, uint32_t advance_by) {
   MT_CHECK_ARG(net && params && obs && ws && batch >= 1, "bad argument");
-  MT_ARCH_SWITCH(net, {
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if constexpr (Ar::LSTM) {
       set_error("the LSTM bootstrap runs through mt_lstm_step_forward");
       return MT_ERR_UNSUPPORTED;
     } else {
-      const WsLayout L = ws_layout<Ar>(net, batch);
-      if (ws_bytes < L.total * sizeof(float)) {
-        set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-        return MT_ERR_WORKSPACE;
-      }
+      MT_TRY(checked_layout<Ar>(net, batch, ws_bytes));
       return forward_boot_impl<Ar>(net, params, obs, batch, (float *)ws, stream, st, advance, advance_by);
     }
   });
-  return MT_OK;
 }
 
 extern "C" int mt_loss_backward(const mt_net *net, const float *params, const uint8_t *obs,
@@ -2042,40 +970,80 @@ extern "C" int mt_loss_backward(const mt_net *net, const float *params, const ui
   MT_CHECK_ARG(net && params && obs && ws && pi && rep && v && a_idx && r_idx && y && adv && grad,
                "null argument");
   MT_CHECK_ARG(batch >= 1, "batch must be >= 1");
-  MT_ARCH_SWITCH(net, {
-    const WsLayout L = ws_layout<Ar>(net, batch);
-    if (ws_bytes < L.total * sizeof(float)) {
-      set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-      return MT_ERR_WORKSPACE;
-    }
+  const LossArgs la{pi, rep, v, a_idx, r_idx, y, adv, entropy_beta, grad, loss_terms};
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(checked_layout<Ar>(net, batch, ws_bytes));
     if constexpr (Ar::LSTM)
-      return lstm_backward_impl<Ar>(net, params, obs, batch, (float *)ws, pi, rep, v, a_idx, r_idx, y, adv,
-                                    entropy_beta, grad, loss_terms, (hipStream_t)stream);
+      return lstm_backward_impl<Ar>(net, params, obs, batch, (float *)ws, la, (hipStream_t)stream);
     else
-      return backward_impl<Ar>(net, params, obs, batch, (float *)ws, pi, rep, v, a_idx, r_idx, y, adv,
-                               entropy_beta, grad, loss_terms, (hipStream_t)stream);
+      return backward_impl<Ar>(net, params, obs, batch, (float *)ws, la, (hipStream_t)stream);
   });
-  return MT_OK;
 }
 
 extern "C" int mt_dropout_redraw(const mt_net *net, const float *params, int batch, void *ws, size_t ws_bytes,
                                  float *v, float *pi, float *rep, mt_stream_t stream) {
   MT_CHECK_ARG(net && params && ws && v && pi && rep, "null argument");
   MT_CHECK_ARG(batch >= 1, "batch must be >= 1");
-  MT_ARCH_SWITCH(net, {
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if constexpr (Ar::DROP_F == 0) {
       set_error("mt_dropout_redraw: the BAYESIAN arch only");
       return MT_ERR_UNSUPPORTED;
     } else {
-      const WsLayout L = ws_layout<Ar>(net, batch);
-      if (ws_bytes < L.total * sizeof(float)) {
-        set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-        return MT_ERR_WORKSPACE;
-      }
+      WsLayout L;
+      MT_TRY(checked_layout<Ar>(net, batch, ws_bytes, &L));
       return dropout_redraw_impl<Ar>(net, params, batch, (float *)ws, L, v, pi, rep, (hipStream_t)stream);
     }
   });
-  return MT_OK;
+}
+
+// The fused-returns entry points (mt_returns_loss_backward, its _boot form, the BAYESIAN
+// mt_dropout_returns_loss_backward) after their own refusals: the workspace check, the in-kernel scan's
+// sources, the norm partials, the backward. What differs between them:
+struct ReturnsForm {
+  const float *v_boot = nullptr;  // V(s_T)[E], finished; or, _boot: the bootstrap forward's workspace,
+  const void *boot_ws = nullptr;  // whose dense slabs the loss kernel finishes into vt_out[E]
+  size_t boot_ws_bytes = 0;
+  float *vt_out = nullptr;
+  // BAYESIAN: the rollout's values (the advantage's), and the redraw that first writes la's v, pi, rep
+  const float *v_roll = nullptr;
+  float *v_new = nullptr, *pi_new = nullptr, *rep_new = nullptr;
+};
+template <class Ar>
+static int returns_backward(const mt_net *net, const float *params, const uint8_t *obs, int T, int E, void *ws,
+                            size_t ws_bytes, const float *rewards, const float *masks, double gamma, float *y,
+                            float *adv, const LossArgs &la, const ReturnsForm &form, float *norm_partials,
+                            hipStream_t s) {
+  const int batch = T * E;
+  WsLayout L, LB;
+  ReturnsSrc rs;
+  if (form.boot_ws) {
+    MT_TRY(checked_layout_boot<Ar>(net, batch, ws_bytes, &L, E, form.boot_ws_bytes, &LB));
+    MT_CHECK_ARG(Ar::F <= 512, "F > 512");
+    rs.boot_slabs = (const float *)form.boot_ws + LB.fcslab;
+    rs.boot_S = Ar::FUSED_SLABS > 0 ? Ar::FUSED_SLABS : LB.fc_splits;
+    rs.fc_b = params + net->off_fc + (size_t)Ar::FLAT * Ar::F;
+    rs.vt_out = form.vt_out;
+  } else {
+    MT_TRY(checked_layout<Ar>(net, batch, ws_bytes, &L));
+    rs.VT = form.v_boot;
+  }
+  if constexpr (Ar::DROP_F > 0) {
+    // the train step's fresh mask (v', pi', rep'; mask, D and H4 for the backward), then the loss kernel
+    // scans with the ROLLOUT's values for the advantage and takes the critic from v'
+    if (form.v_new)
+      MT_TRY(dropout_redraw_impl<Ar>(net, params, batch, (float *)ws, L, form.v_new, form.pi_new, form.rep_new, s));
+  }
+  rs.r = rewards;
+  rs.mask = masks;
+  rs.gamma = gamma;
+  rs.T = T;
+  rs.E = E;
+  rs.y_out = y;
+  rs.adv_out = adv;
+  rs.v_roll = form.v_roll;
+  return backward_impl<Ar>(net, params, obs, batch, (float *)ws, la, s, rs, NormOut(norm_partials, net));
 }
 
 extern "C" int mt_dropout_returns_loss_backward(const mt_net *net, const float *params, const uint8_t *obs, int T,
@@ -2089,38 +1057,23 @@ extern "C" int mt_dropout_returns_loss_backward(const mt_net *net, const float *
                    pi_out && rep_out && y && adv && grad,
                "null argument");
   MT_CHECK_ARG(T >= 1 && E >= 1 && T <= kMaxScan, "T=%d (<= %d) and E=%d must be >= 1", T, kMaxScan, E);
-  const int batch = T * E;
-  MT_ARCH_SWITCH(net, {
+  const LossArgs la{pi_out, rep_out, v_out, a_idx, r_idx, y, adv, entropy_beta, grad, loss_terms};
+  ReturnsForm form;
+  form.v_boot = v_boot;
+  form.v_roll = values;
+  form.v_new = v_out;
+  form.pi_new = pi_out;
+  form.rep_new = rep_out;
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if constexpr (Ar::DROP_F == 0) {
       set_error("mt_dropout_returns_loss_backward: the BAYESIAN arch only");
       return MT_ERR_UNSUPPORTED;
     } else {
-      const WsLayout L = ws_layout<Ar>(net, batch);
-      if (ws_bytes < L.total * sizeof(float)) {
-        set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-        return MT_ERR_WORKSPACE;
-      }
-      // the train step's fresh mask (v', pi', rep'; mask, D and H4 for the backward), then the loss kernel
-      // scans with the ROLLOUT's values for the advantage and takes the critic from v'
-      MT_TRY(dropout_redraw_impl<Ar>(net, params, batch, (float *)ws, L, v_out, pi_out, rep_out, (hipStream_t)stream));
-      ReturnsSrc rs;
-      rs.r = rewards;
-      rs.mask = masks;
-      rs.VT = v_boot;
-      rs.gamma = gamma;
-      rs.T = T;
-      rs.E = E;
-      rs.y_out = y;
-      rs.adv_out = adv;
-      rs.v_roll = values;
-      NormOut no;
-      no.partials = norm_partials;
-      no.n = net->nparams;
-      return backward_impl<Ar>(net, params, obs, batch, (float *)ws, pi_out, rep_out, v_out, a_idx, r_idx, y, adv,
-                               entropy_beta, grad, loss_terms, (hipStream_t)stream, rs, no);
+      return returns_backward<Ar>(net, params, obs, T, E, ws, ws_bytes, rewards, masks, gamma, y, adv, la, form,
+                                  norm_partials, (hipStream_t)stream);
     }
   });
-  return MT_OK;
 }
 
 extern "C" int mt_dropout_mask_host(uint64_t seed, uint64_t global_row, uint64_t counter, float keep_prob,
@@ -2142,8 +1095,11 @@ extern "C" int mt_returns_loss_backward(const mt_net *net, const float *params, 
                    y && adv && grad,
                "null argument");
   MT_CHECK_ARG(T >= 1 && E >= 1 && T <= kMaxScan, "T=%d (<= %d) and E=%d must be >= 1", T, kMaxScan, E);
-  const int batch = T * E;
-  MT_ARCH_SWITCH(net, {
+  const LossArgs la{pi, rep, values, a_idx, r_idx, y, adv, entropy_beta, grad, loss_terms};
+  ReturnsForm form;
+  form.v_boot = v_boot;
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if constexpr (Ar::LSTM) {
       set_error("mt_returns_loss_backward: the LSTM arch trains through mt_lstm_frames_backward");
       return MT_ERR_UNSUPPORTED;
@@ -2153,28 +1109,10 @@ extern "C" int mt_returns_loss_backward(const mt_net *net, const float *params, 
                 "mt_loss_backward");
       return MT_ERR_UNSUPPORTED;
     } else {
-      const WsLayout L = ws_layout<Ar>(net, batch);
-      if (ws_bytes < L.total * sizeof(float)) {
-        set_error("workspace %zu < %zu bytes", ws_bytes, L.total * sizeof(float));
-        return MT_ERR_WORKSPACE;
-      }
-      ReturnsSrc rs;
-      rs.r = rewards;
-      rs.mask = masks;
-      rs.VT = v_boot;
-      rs.gamma = gamma;
-      rs.T = T;
-      rs.E = E;
-      rs.y_out = y;
-      rs.adv_out = adv;
-      NormOut no;
-      no.partials = norm_partials;
-      no.n = net->nparams;
-      return backward_impl<Ar>(net, params, obs, batch, (float *)ws, pi, rep, values, a_idx, r_idx, y, adv,
-                               entropy_beta, grad, loss_terms, (hipStream_t)stream, rs, no);
+      return returns_backward<Ar>(net, params, obs, T, E, ws, ws_bytes, rewards, masks, gamma, y, adv, la, form,
+                                  norm_partials, (hipStream_t)stream);
     }
   });
-  return MT_OK;
 }
 
 extern "C" int mt_returns_loss_backward_boot(const mt_net *net, const float *params, const uint8_t *obs, int T, int E,
@@ -2188,8 +1126,13 @@ extern "C" int mt_returns_loss_backward_boot(const mt_net *net, const float *par
                    v_boot && y && adv && grad,
                "null argument");
   MT_CHECK_ARG(T >= 1 && E >= 1 && T <= kMaxScan, "T=%d (<= %d) and E=%d must be >= 1", T, kMaxScan, E);
-  const int batch = T * E;
-  MT_ARCH_SWITCH(net, {
+  const LossArgs la{pi, rep, values, a_idx, r_idx, y, adv, entropy_beta, grad, loss_terms};
+  ReturnsForm form;
+  form.boot_ws = boot_ws;
+  form.boot_ws_bytes = boot_ws_bytes;
+  form.vt_out = v_boot;
+  return with_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
     if constexpr (Ar::LSTM) {
       set_error("mt_returns_loss_backward_boot: the LSTM arch trains through mt_lstm_frames_backward");
       return MT_ERR_UNSUPPORTED;
@@ -2198,70 +1141,45 @@ extern "C" int mt_returns_loss_backward_boot(const mt_net *net, const float *par
                 "and mt_loss_backward");
       return MT_ERR_UNSUPPORTED;
     } else {
-      const WsLayout L = ws_layout<Ar>(net, batch);
-      const WsLayout LB = ws_layout<Ar>(net, E);
-      if (ws_bytes < L.total * sizeof(float) || boot_ws_bytes < LB.total * sizeof(float)) {
-        set_error("workspace %zu / bootstrap workspace %zu < %zu / %zu bytes", ws_bytes, boot_ws_bytes,
-                  L.total * sizeof(float), LB.total * sizeof(float));
-        return MT_ERR_WORKSPACE;
-      }
-      MT_CHECK_ARG(Ar::F <= 512, "F > 512");
-      ReturnsSrc rs;
-      rs.r = rewards;
-      rs.mask = masks;
-      rs.gamma = gamma;
-      rs.T = T;
-      rs.E = E;
-      rs.y_out = y;
-      rs.adv_out = adv;
-      rs.boot_slabs = (const float *)boot_ws + LB.fcslab;
-      rs.boot_S = Ar::FUSED_SLABS > 0 ? Ar::FUSED_SLABS : LB.fc_splits;
-      rs.fc_b = params + net->off_fc + (size_t)Ar::FLAT * Ar::F;
-      rs.vt_out = v_boot;
-      NormOut no;
-      no.partials = norm_partials;
-      no.n = net->nparams;
-      return backward_impl<Ar>(net, params, obs, batch, (float *)ws, pi, rep, values, a_idx, r_idx, y, adv,
-                               entropy_beta, grad, loss_terms, (hipStream_t)stream, rs, no);
+      return returns_backward<Ar>(net, params, obs, T, E, ws, ws_bytes, rewards, masks, gamma, y, adv, la, form,
+                                  norm_partials, (hipStream_t)stream);
     }
   });
-  return MT_OK;
 }
 
 // ---- LSTM frame-store mode (lstm.h) ----------------------------------------------------------
-#define MT_LSTM_ONLY(net, ...)                                                  \
-  MT_ARCH_SWITCH(net, {                                                         \
-    if constexpr (Ar::LSTM) {                                                   \
-      __VA_ARGS__;                                                              \
-    } else {                                                                    \
-      set_error("frame-store calls need the LSTM arch");                        \
-      return MT_ERR_ARG;                                                        \
-    }                                                                           \
-  })
-
-#define MT_LSTM_WS(E, T)                                                        \
-  const LstmFrameWs X_ = lstm_frame_layout<Ar>(net, E, T);                      \
-  if (ws_bytes < X_.L.total * sizeof(float)) {                                  \
-    set_error("workspace %zu < %zu bytes", ws_bytes, X_.L.total * sizeof(float)); \
-    return MT_ERR_WORKSPACE;                                                    \
-  }
+// with_arch for the frame-store calls: the LSTM archs only.
+template <class Fn>
+static int with_lstm_arch(const mt_net *net, const Fn &fn) {
+  return with_arch(net, [&](auto ar) -> int {
+    if constexpr (decltype(ar)::LSTM) {
+      return fn(ar);
+    } else {
+      set_error("frame-store calls need the LSTM arch");
+      return MT_ERR_ARG;
+    }
+  });
+}
 
 extern "C" int mt_lstm_frames_workspace_bytes(const mt_net *net, int E, int T, size_t *bytes) {
   MT_CHECK_ARG(net && bytes, "null argument");
   MT_CHECK_ARG(E >= 1 && T >= 1, "E and T must be >= 1");
-  MT_LSTM_ONLY(net, { *bytes = lstm_frame_layout<Ar>(net, E, T).L.total * sizeof(float); });
-  return MT_OK;
+  return with_lstm_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    *bytes = lstm_frame_layout<Ar>(net, E, T).L.total * sizeof(float);
+    return MT_OK;
+  });
 }
 
 extern "C" int mt_lstm_frames_forward(const mt_net *net, const float *params, const uint8_t *fstore, int row0,
                                       int nrows, int E, int T, void *ws, size_t ws_bytes, mt_stream_t stream) {
   MT_CHECK_ARG(net && params && fstore && ws, "null argument");
   MT_CHECK_ARG(E >= 1 && T >= 1, "E and T must be >= 1");
-  MT_LSTM_ONLY(net, {
-    MT_LSTM_WS(E, T);
+  return with_lstm_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(check_ws(ws_bytes, lstm_frame_layout<Ar>(net, E, T).L));
     return lstm_frames_fwd_impl<Ar>(net, params, fstore, row0, nrows, E, T, (float *)ws, (hipStream_t)stream);
   });
-  return MT_OK;
 }
 
 extern "C" int mt_lstm_windows_forward(const mt_net *net, const float *params, const int32_t *nz_t, int t, int E,
@@ -2269,13 +1187,13 @@ extern "C" int mt_lstm_windows_forward(const mt_net *net, const float *params, c
                                        mt_stream_t stream) {
   MT_CHECK_ARG(net && params && nz_t && ws && v && pi && rep, "null argument");
   MT_CHECK_ARG(E >= 1 && T >= 1, "E and T must be >= 1");
-  MT_LSTM_ONLY(net, {
-    MT_LSTM_WS(E, T);
+  return with_lstm_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(check_ws(ws_bytes, lstm_frame_layout<Ar>(net, E, T).L));
     // (nz_t is only read: no nz_prev)
     return lstm_windows_fwd_impl<Ar>(net, params, const_cast<int32_t *>(nz_t), t, E, T, (float *)ws, v, pi, rep,
                                      (hipStream_t)stream);
   });
-  return MT_OK;
 }
 
 extern "C" int mt_lstm_step_forward(const mt_net *net, const float *params, const uint8_t *fstore, int t, int E,
@@ -2292,12 +1210,12 @@ int mt::lstm_step_forward(const mt_net *net, const float *params, const uint8_t 
                           const SampleArgs *smp, hipStream_t stream, const hipEvent_t *marks, const StackSrc *st,
                           uint32_t *sync) {
   MT_CHECK_ARG(!smp || (smp->counters && smp->a_idx && smp->r_idx), "null sample buffer");
-  MT_LSTM_ONLY(net, {
-    MT_LSTM_WS(E, T);
+  return with_lstm_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(check_ws(ws_bytes, lstm_frame_layout<Ar>(net, E, T).L));
     return lstm_step_fwd_impl<Ar>(net, params, fstore, t, E, T, nz, over, (float *)ws, v, pi, rep, smp, stream,
                                   marks, st, sync);
   });
-  return MT_OK;
 }
 
 extern "C" int mt_lstm_frames_backward(const mt_net *net, const float *params, const uint8_t *fstore,
@@ -2308,15 +1226,13 @@ extern "C" int mt_lstm_frames_backward(const mt_net *net, const float *params, c
   MT_CHECK_ARG(net && params && fstore && nz && ws && pi && rep && v && a_idx && r_idx && y && adv && grad,
                "null argument");
   MT_CHECK_ARG(E >= 1 && T >= 1, "E and T must be >= 1");
-  MT_LSTM_ONLY(net, {
-    MT_LSTM_WS(E, T);
-    NormOut no;
-    no.partials = norm_partials;
-    no.n = net->nparams;
-    return lstm_frames_bwd_impl<Ar>(net, params, fstore, nz, E, T, (float *)ws, pi, rep, v, a_idx, r_idx, y, adv,
-                                    entropy_beta, grad, loss_terms, (hipStream_t)stream, no);
+  const LossArgs la{pi, rep, v, a_idx, r_idx, y, adv, entropy_beta, grad, loss_terms};
+  return with_lstm_arch(net, [&](auto ar) -> int {
+    using Ar = decltype(ar);
+    MT_TRY(check_ws(ws_bytes, lstm_frame_layout<Ar>(net, E, T).L));
+    return lstm_frames_bwd_impl<Ar>(net, params, fstore, nz, E, T, (float *)ws, la, (hipStream_t)stream,
+                                    NormOut(norm_partials, net));
   });
-  return MT_OK;
 }
 
 // mt_sum_slabs for slabs that are not rows of float4s (n not a multiple of 4, or unaligned
@@ -2342,5 +1258,5 @@ extern "C" int mt_sum_slabs(const float *parts, int nslabs, size_t n, float *out
     MT_LAUNCHED();
     return MT_OK;
   }
-  return sum_slabs(parts, nslabs, n, out, (hipStream_t)stream);
+  return launch_group((hipStream_t)stream, SlabJob{parts, nslabs, n, out});
 }

@@ -19,6 +19,14 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _addr(x):
+    """A tensor's pointer, or a device address passed as an int or a c_void_p (e.g. of pinned,
+    device-mapped host memory)."""
+    if isinstance(x, C.c_void_p):
+        return x
+    return C.c_void_p(x) if isinstance(x, int) else _ptr(x)
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -267,10 +275,9 @@ class DeviceNetwork(object):
         B = int(T) * int(E)
         ws = self.workspace(B, ws_key)
         v, pi, rep = out
-        addr = lambda x: C.c_void_p(x) if isinstance(x, int) else _ptr(x)
         check(_lib.hip().mt_dropout_returns_loss_backward(
             self._h, _ptr(self.params), _ptr(obs), int(T), int(E), _ptr(ws), ws.numel(), _ptr(values), _ptr(a_idx),
-            _ptr(r_idx), addr(rewards), addr(masks), _ptr(v_boot), float(gamma), _ptr(v), _ptr(pi), _ptr(rep),
+            _ptr(r_idx), _addr(rewards), _addr(masks), _ptr(v_boot), float(gamma), _ptr(v), _ptr(pi), _ptr(rep),
             _ptr(y), _ptr(adv), self.beta, _ptr(self.grad), _ptr(loss_terms),
             _ptr(self.partials if norm_partials else None), _stream()), 'mt_dropout_returns_loss_backward')
         return self.grad
@@ -314,8 +321,7 @@ class DeviceNetwork(object):
         env's frames behind its ready word), diagnostics / parity / roofline timing. status: a
         WaitStatus whose word a timed-out device wait sets (check it once the stream completed)."""
         ws = self.workspace(batch, ws_key)
-        addr = lambda x: x if isinstance(x, C.c_void_p) else _ptr(x)
-        check(_lib.hip().mt_forward_trunk_stacking(self._h, _ptr(self.params), _ptr(prev), addr(frames), addr(ready),
+        check(_lib.hip().mt_forward_trunk_stacking(self._h, _ptr(self.params), _ptr(prev), _addr(frames), _addr(ready),
                                                    C.c_uint32(tag), _ptr(out), int(batch), _ptr(ws), ws.numel(),
                                                    C.c_void_p(status.dev) if status is not None else None,
                                                    _stream()), 'mt_forward_trunk_stacking')
@@ -395,17 +401,16 @@ class DeviceNetwork(object):
         (mt_returns_loss_backward_boot)."""
         B = T * E
         ws = self.workspace(B, ws_key)
-        addr = lambda x: C.c_void_p(x) if isinstance(x, int) else _ptr(x)
         if boot_ws is not None:
             check(_lib.hip().mt_returns_loss_backward_boot(
                 self._h, _ptr(self.params), _ptr(obs), int(T), int(E), _ptr(ws), ws.numel(), _ptr(pi), _ptr(rep),
-                _ptr(values), _ptr(a_idx), _ptr(r_idx), addr(rewards), addr(masks), _ptr(boot_ws), boot_ws.numel(),
+                _ptr(values), _ptr(a_idx), _ptr(r_idx), _addr(rewards), _addr(masks), _ptr(boot_ws), boot_ws.numel(),
                 _ptr(v_boot), float(gamma), _ptr(y), _ptr(adv), self.beta, _ptr(self.grad), _ptr(loss_terms),
                 _ptr(self.partials if norm_partials else None), _stream()), 'mt_returns_loss_backward_boot')
             return self.grad
         check(_lib.hip().mt_returns_loss_backward(
             self._h, _ptr(self.params), _ptr(obs), int(T), int(E), _ptr(ws), ws.numel(), _ptr(pi), _ptr(rep),
-            _ptr(values), _ptr(a_idx), _ptr(r_idx), addr(rewards), addr(masks), _ptr(v_boot), float(gamma), _ptr(y),
+            _ptr(values), _ptr(a_idx), _ptr(r_idx), _addr(rewards), _addr(masks), _ptr(v_boot), float(gamma), _ptr(y),
             _ptr(adv), self.beta, _ptr(self.grad), _ptr(loss_terms), _ptr(self.partials if norm_partials else None),
             _stream()), 'mt_returns_loss_backward')
         return self.grad
@@ -473,8 +478,7 @@ def returns(rewards, masks, values, v_boot, gamma, y, adv):
     """paac.py:219-231 on device. rewards / masks: [T][E] device tensors, or device addresses
     (e.g. of pinned, device-mapped host memory the kernel reads in place)."""
     T, E = values.shape
-    addr = lambda x: C.c_void_p(x) if isinstance(x, int) else _ptr(x)
-    check(_lib.hip().mt_returns(addr(rewards), addr(masks), _ptr(values), _ptr(v_boot), float(gamma),
+    check(_lib.hip().mt_returns(_addr(rewards), _addr(masks), _ptr(values), _ptr(v_boot), float(gamma),
                                 T, E, _ptr(y), _ptr(adv), _stream()), 'mt_returns')
 
 
