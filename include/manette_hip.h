@@ -708,6 +708,65 @@ int mt_catch_step_host(const mt_catch_config *cfg, uint64_t seed, uint64_t globa
                        uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out,
                        float *over_out);
 
+/* ---- Device bookkeeping of one rollout (the learner's Bookkeeper.step, paac.py:154-205, as a kernel) ----
+ * Everything a rollout of a device-resident game leaves for the host (global_step, the episode records,
+ * the action / repetition histogram, the learning rate of its update) computed where the rollout ran, so
+ * a training iteration needs no host synchronisation. The rule, for t = 0 .. T-1 in order, with
+ * a = a_idx[t][e] clamped to [0, A-1] and r = r_idx[t][e] clamped to [0, R-1] (as the env kernel clamps):
+ *
+ *   per env e  total_episode_rewards[e] += reward[t][e] (one fp32 add);
+ *              emulator_steps[e] += tab_rep[r] + 1 (the planned repeats, tab_rep as given);
+ *              where over[t][e] != 0: append the record {global_step + env_offset + e + 1,
+ *              emulator_steps[e], total_episode_rewards[e]} and zero both accumulators.
+ *   order      the records of one step are appended in env order, steps in t order, record k of the
+ *              book's life at ring slot k % capacity (k = words->written, which counts them).
+ *   then       global_step += envs_total.
+ *   after T-1  hist[a][r] = the number of (t, e) pairs that drew (a, r) and nb_actions = the sum of r + 1
+ *              over the pairs: of THIS rollout (written, not accumulated); and, for g = (double)global_step,
+ *              *lr = (float)(g <= lr_annealing_steps ? initial_lr - (g * initial_lr / lr_annealing_steps)
+ *              : 0.0): a product, a quotient, a difference in double, rounded once to float
+ *              (actor_learner.py:get_lr as the native rollout restates it).
+ *   overflow   if the rollout's records would make written - acked exceed capacity, NONE of them is
+ *              appended (the accumulators still advance and reset as the rule says), words->overflow is
+ *              set to 1 and stays set; global_step, hist, nb_actions and *lr are written as ever.
+ *              Nothing is overwritten. The host acknowledges records by storing acked = written.
+ *
+ * One workgroup; no atomics, no float reductions; allocates nothing, does not synchronise, capturable.
+ * Every pointer is device memory (mt_book_rollout) or host memory (mt_book_rollout_host, the same rule
+ * with no GPU; the kernel is pinned against it). a_idx, r_idx: [T][E] int32; reward, over: [T][E] fp32
+ * (the unclipped sums and 0/1 flags of the env kernel); tab_rep: [R] int32. MT_ERR_ARG before any launch
+ * for a null pointer, A, R, E or T < 1, capacity < 1, env_offset < 0, envs_total < env_offset + E, or
+ * lr_annealing_steps <= 0. */
+typedef struct mt_book_words {
+  int64_t global_step;
+  int64_t written;    /* episode records appended so far (monotonic) */
+  int64_t acked;      /* stored by the host at a drain */
+  int64_t nb_actions; /* of the last rollout */
+  int32_t overflow;
+  int32_t reserved;
+} mt_book_words;
+typedef struct mt_book_episode {
+  int64_t global_step;
+  int64_t length;
+  float reward;
+  int32_t reserved;
+} mt_book_episode;
+typedef struct mt_book_state {
+  float *total_episode_rewards; /* [E] */
+  int64_t *emulator_steps;      /* [E] */
+  mt_book_words *words;
+  int64_t *hist;                /* [A][R] */
+  float *lr;                    /* the word mt_clip_rmsprop reads through lr_dev */
+  mt_book_episode *ring;        /* [capacity] */
+  int64_t capacity;
+} mt_book_state;
+int mt_book_rollout(const mt_book_state *book, const int32_t *a_idx, const int32_t *r_idx, const float *reward,
+                    const float *over, const int32_t *tab_rep, int A, int R, int E, int T, int64_t env_offset,
+                    int64_t envs_total, double initial_lr, double lr_annealing_steps, mt_stream_t stream);
+int mt_book_rollout_host(const mt_book_state *book, const int32_t *a_idx, const int32_t *r_idx, const float *reward,
+                         const float *over, const int32_t *tab_rep, int A, int R, int E, int T, int64_t env_offset,
+                         int64_t envs_total, double initial_lr, double lr_annealing_steps);
+
 #ifdef __cplusplus
 }
 #endif

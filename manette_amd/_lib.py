@@ -70,6 +70,22 @@ class mt_catch_state(C.Structure):
                [('ball_counter', C.c_uint64)]
 
 
+class mt_book_words(C.Structure):
+    """The device book's word block (include/manette_hip.h, "Device bookkeeping"), 40 bytes."""
+    _fields_ = [(n, C.c_int64) for n in ('global_step', 'written', 'acked', 'nb_actions')] + \
+               [('overflow', C.c_int32), ('reserved', C.c_int32)]
+
+
+class mt_book_episode(C.Structure):
+    """One episode record of the device book's ring, 24 bytes."""
+    _fields_ = [('global_step', C.c_int64), ('length', C.c_int64), ('reward', C.c_float), ('reserved', C.c_int32)]
+
+
+class mt_book_state(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('total_episode_rewards', 'emulator_steps', 'words', 'hist', 'lr', 'ring')] + \
+               [('capacity', C.c_int64)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -154,6 +170,10 @@ _HIP_SIGS = {
     'mt_catch_step_host': (_I, [C.POINTER(mt_catch_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
                                 C.POINTER(mt_catch_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
                                 C.POINTER(_F)]),
+    'mt_book_rollout': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
+                             C.c_double, C.c_double, _P]),
+    'mt_book_rollout_host': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
+                                  C.c_double, C.c_double]),
 }
 
 _HOST_SIGS = {

@@ -420,17 +420,19 @@ class DeviceNetwork(object):
         kernel reads in place (no copy; a captured graph also picks up the schedule)."""
         self._lr_host[0] = float(lr)
 
-    def apply_gradients(self, inv_scale=1.0, partials_ready=False):
+    def apply_gradients(self, inv_scale=1.0, partials_ready=False, lr_addr=None):
         """clip_by_global_norm + ApplyRMSProp on self.grad (actor_learner.py:47-74).
         inv_scale folds the 1/world of a data-parallel gradient sum. partials_ready: the backward
-        already wrote the norm partials (returns_loss_backward(norm_partials=True), inv_scale 1)."""
+        already wrote the norm partials (returns_loss_backward(norm_partials=True), inv_scale 1).
+        lr_addr: device address of the fp32 LR word the kernel reads (default: the pinned word of set_lr)."""
         lib = _lib.hip()
         s = _stream()
         if not partials_ready:
             check(lib.mt_grad_sumsq(_ptr(self.grad), self.nparams, float(inv_scale), _ptr(self.partials), s),
                   'mt_grad_sumsq')
         check(lib.mt_clip_rmsprop(_ptr(self.params), _ptr(self.ms), _ptr(self.mom), _ptr(self.grad),
-                                  self.nparams, _ptr(self.partials), C.c_void_p(self._lr_dev_addr), self.decay, 0.0,
+                                  self.nparams, _ptr(self.partials),
+                                  C.c_void_p(self._lr_dev_addr if lr_addr is None else lr_addr), self.decay, 0.0,
                                   self.eps, self.clip_norm, self.clip_type, float(inv_scale),
                                   _ptr(self.norm_dev), s), 'mt_clip_rmsprop')
 

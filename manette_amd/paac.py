@@ -13,7 +13,9 @@ Paths (args.runner):
             84x84xC observations go H2D.
   'device'  the game itself lives in HBM (-g catch, manette_amd/catch.py): one kernel per macro-step
             steps, renders and stacks every env (mt_catch_step); with --sampling device a rollout is
-            T x (forward -> draw -> env kernel) enqueued without a host synchronisation (_device_rollout).
+            T x (forward -> draw -> env kernel) enqueued without a host synchronisation (_device_rollout);
+            with --iteration_graph the rollout's bookkeeping is a kernel as well (mt_book_rollout, DeviceBook)
+            and rollout + update are one graph replayed per iteration, drained every --drain_every (_iteration).
 Sampling (args.sampling): 'host' = the reference's numpy multinomial stream (parity mode),
 'device' = mt_sample (perf mode, same distribution), or with --egreedy / a test policy the e-greedy /
 argmax draw of mt_policy (mt_sample_policy, mt_rollout_set_policy), epsilon annealed on the device.
@@ -68,6 +70,27 @@ def check_arch_flags(args):
             raise ValueError('--runner device runs the BAYESIAN Python-step form: drop --bayes_native')
     elif runner == 'native' and has_device_env(game):
         raise ValueError('-g %s runs under --runner device or --runner python, not the native runner' % game)
+    # --iteration_graph: a whole training iteration of the device game as one replayed graph, its
+    # bookkeeping on the device (mt_book_rollout); nothing of an iteration may live on the host
+    if getattr(args, 'iteration_graph', False):
+        arch = getattr(args, 'arch', None)
+        if runner != 'device' or getattr(args, 'sampling', 'host') != 'device':
+            raise ValueError('--iteration_graph needs --runner device --sampling device: with --runner %s --sampling %s '
+                             'the emulators or the draw run on the host' % (runner, getattr(args, 'sampling', 'host')))
+        if arch == 'BAYESIAN':
+            raise ValueError('--iteration_graph does not serve --arch BAYESIAN: its mask counter is host state, a '
+                             'replayed graph would reuse one dropout mask')
+        if arch == 'LSTM':
+            raise ValueError('--iteration_graph does not serve --arch LSTM (its frame store is filled by the host path)')
+        import torch
+        world = torch.distributed.get_world_size() if (torch.distributed.is_available()
+                                                       and torch.distributed.is_initialized()) else 1
+        world = max(world, int(os.environ.get('WORLD_SIZE', '1')))
+        if world > 1 or getattr(args, 'dp_force', False) or os.environ.get('MT_DP_FORCE') == '1':
+            raise ValueError('--iteration_graph is single-process (world 1): the data-parallel all-reduce is issued '
+                             'by the host between graphs')
+        if getattr(args, 'drain_every', None) is not None and int(args.drain_every) < 1:
+            raise ValueError('--drain_every must be >= 1')
 
 
 class PAACLearner(ActorLearner):
@@ -187,7 +210,21 @@ class PAACLearner(ActorLearner):
         self.row_lut = torch.from_numpy(ROW_LUT.astype(np.int32)).to(dev)
         self.col_lut = torch.from_numpy(COL_LUT.astype(np.int32)).to(dev)
         self.event = torch.cuda.Event()
-        self.book = NativeBook(E, self.num_actions, self.tab_rep)
+        # --iteration_graph (device game, device draw): rollout + bookkeeping + update as one graph
+        # replayed per iteration, drained every drain_every iterations (_iteration, _train_graph)
+        self.iteration_graph = bool(getattr(args, 'iteration_graph', False))
+        self.drain_every = int(getattr(args, 'drain_every', None) or max(1, 2048 // E))
+        self._lr_addr = None  # the LR word of clip + RMSProp when it is not the network's pinned one
+        self._iter_graph = None
+        self._iterations = 0
+        if self.iteration_graph:
+            from .bookkeeping import DeviceBook
+            # a drain follows at most drain_every iterations: their T*E possible records always fit
+            self.book = DeviceBook(E, self.num_actions, self.tab_rep, self.drain_every * T * E, self.initial_lr,
+                                   self.lr_annealing_steps, device=dev, event=self.event)
+            self._lr_addr = self.book.lr_addr
+        else:
+            self.book = NativeBook(E, self.num_actions, self.tab_rep)
         if self.world > 1:  # global_step counts every env of the job, as one process would
             self.book.set_shard(self.env_offset, E * self.world)
         self.native_step = None  # mt_rollout handle (native runner + device sampling)
@@ -277,6 +314,8 @@ class PAACLearner(ActorLearner):
             self.ro_d = torch.zeros(2, T, E, dtype=torch.float32, device=self.dev)  # [0] rewards, [1] over flags
             self.ro_h = torch.zeros(2, T, E, dtype=torch.float32, pin_memory=True)
             self.env.reset(self.states[0])
+            if self.iteration_graph:
+                self.book.set_global_step(self.global_step)
         else:
             emus = [self.environment_creator.create_environment(i) for i in range(E)]
             s0 = np.asarray([e.get_initial_state() for e in emus], dtype=np.uint8)
@@ -393,10 +432,71 @@ class PAACLearner(ActorLearner):
                                                  self._lib_ref(self._gs), devnet._stream()), 'mt_rollout_run')
             self.global_step = self._gs.value
             return
+        if self.iteration_graph:
+            return self._iteration()
         if self.runner_kind == 'device' and self.sampling == 'device':
             return self._device_rollout()
         for t in range(self.max_local_steps):
             self.step(t)
+
+    def _iteration_work(self):
+        """The device work of one training iteration under --iteration_graph, nothing of it on the host:
+        T x (forward -> draw -> env kernel), the bookkeeping of the rollout (mt_book_rollout: global_step,
+        episode records, histogram, the LR word), the bootstrap forward, the fused returns + loss backward,
+        clip + RMSProp reading the book's LR word, states[T] -> states[0]."""
+        net = self.network
+        E, T = self.emulator_counts, self.max_local_steps
+        for t in range(T):
+            _, pi, rep = net.forward_rows(self.states[t], E, self.train_ws, T * E, t * E,
+                                          out=(self.values[t], self.pi_all[t], self.rep_all[t]), ws_key='rollout')
+            devnet.sample(pi, rep, self.sample_seed, self.counters, self.a_idx[t], self.r_idx[t], row0=self.env_offset,
+                          policy=self.policy)
+            self.env.step(self.a_idx[t], self.r_idx[t], self.states[t], self.states[t + 1], self.ro_d[0, t],
+                          self.ro_d[1, t], self.rm_d, t, T)
+        self.book.rollout(self.a_idx, self.r_idx, self.ro_d[0], self.ro_d[1], T)
+        self._update_backward()
+        self._update_apply()
+
+    def _iteration(self):
+        """One iteration: the first runs eagerly (workspaces are made), the second is captured
+        (mt_graph_begin / mt_graph_end; nothing executes while capturing) and launched, later ones are
+        replays: one mt_graph_launch and no host synchronisation. The host mirrors global_step (it
+        advances by T * envs_total per iteration); drain() checks the mirror against the device word."""
+        if self._iter_graph is None and self._iterations >= 1 and self.use_update_graph and self.profile is None:
+            self._capture_iteration()
+        if self._iter_graph is not None:
+            self._launch_graph(self._iter_graph, devnet._stream())
+        else:
+            self._iteration_work()
+        self._iterations += 1
+        self.global_step += self.max_local_steps * self.book.envs_total
+
+    def _capture_iteration(self):
+        import ctypes as C
+        from . import _lib
+        lib = _lib.hip()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        with torch.cuda.stream(side):
+            sp = devnet._stream()
+            _lib.check(lib.mt_graph_begin(sp), 'mt_graph_begin')
+            try:
+                self._iteration_work()
+            finally:
+                g = C.c_void_p()
+                rc = lib.mt_graph_end(sp, C.byref(g))
+            _lib.check(rc, 'mt_graph_end')
+        self._iter_graph = g
+        self._graph_stream = side  # keep the capture stream alive with the graph
+
+    def drain(self):
+        """--iteration_graph: the host catches up with the device book (one D2H copy, one synchronisation):
+        episode records, the last histogram, and the device global_step, which must equal the mirror."""
+        gs = self.book.drain()
+        if gs != self.global_step:
+            raise RuntimeError('device global_step %d != the host mirror %d' % (gs, self.global_step))
+        return gs
 
     def _device_rollout(self):
         """Device env + device draw: T x (forward -> draw -> env kernel) enqueued with no host
@@ -524,6 +624,8 @@ class PAACLearner(ActorLearner):
         With --bayes_native: [bootstrap forward unless the rollout ran it], the one-call backward
         (mt_dropout_returns_loss_backward), clip + RMSProp, captured after the first eager update: one
         graph the rollout's last step launches, or at world > 1 backward | eager all-reduce | apply."""
+        if self.iteration_graph:  # rollout() ran the whole iteration; the LR it used, from the mirror
+            return self.get_lr()
         self.book.drain()
         lr = self.get_lr()
         if self._update_in_rollout:  # the rollout's last step stored lr and launched the update graph
@@ -668,7 +770,8 @@ class PAACLearner(ActorLearner):
         T = self.max_local_steps
         # (the LSTM / fused-returns backwards leave the norm partials; BAYESIAN's mt_loss_backward does not)
         self.network.apply_gradients(self.grad_scale,
-                                     partials_ready=not self.dp and (not self.bayes_bool or self.bayes_native))
+                                     partials_ready=not self.dp and (not self.bayes_bool or self.bayes_native),
+                                     lr_addr=self._lr_addr)
         if self.lstm_bool:  # the next rollout's slots 0..4 = s_{T-4} .. s_T; windows carry over
             if T >= 5:
                 self.slots[0:5].copy_(self.slots[T:T + 5])
@@ -851,6 +954,10 @@ class PAACLearner(ActorLearner):
             for g in self._graphs:
                 _lib.hip().mt_graph_destroy(g)
         self._graphs = None
+        if getattr(self, '_iter_graph', None) is not None:
+            from . import _lib
+            _lib.hip().mt_graph_destroy(self._iter_graph)
+        self._iter_graph = None
 
     def loss_value(self):
         """5*(mean(-(adv*logp + beta*H)) + mean(0.25(y-v)^2)) of the last update (host sync)."""
@@ -939,6 +1046,8 @@ class PAACLearner(ActorLearner):
         counter = 0
         start_time = time.time()
         logging.debug('Starting training at Step %d', self.global_step)
+        if self.iteration_graph:
+            return self._train_graph(start_time)
         try:
             while self.global_step < self.max_global_steps:
                 loop_start_time = time.time()
@@ -966,6 +1075,34 @@ class PAACLearner(ActorLearner):
                 self.save_vars()
             if self.world > 1:  # (every rank: a collective) the episodes since the last gather
                 self._write_summaries_dp(final=True)
+        finally:
+            self.cleanup()
+
+    def _train_graph(self, start_time):
+        """train() under --iteration_graph: up to drain_every iterations launched back to back (the host
+        does nothing else between drains), then one drain, at which the summaries, the log line and
+        save_vars run: a checkpoint lands on a drain boundary. The iteration count comes from the
+        mirror, so the run performs exactly the updates of the eager loop."""
+        per = self.max_local_steps * self.book.envs_total
+        counter, log_every = 0, max(1, 2048 // self.emulator_counts)
+        try:
+            while self.global_step < self.max_global_steps:
+                loop_start_time = time.time()
+                n = min(self.drain_every, -(-(self.max_global_steps - self.global_step) // per))
+                for _ in range(n):
+                    self._iteration()
+                self.drain()
+                self.write_summaries()
+                if (counter + n) // log_every > counter // log_every:
+                    now = time.time()
+                    tr = self.book.total_rewards
+                    last_ten = 0.0 if len(tr) < 1 else float(np.mean(tr[-10:]))
+                    steps_per_sec = n * per / (now - loop_start_time)
+                    avg = (self.global_step - self.global_step_start) / (now - start_time)
+                    logging.info('Ran %d steps, at %f steps/s (%f steps/s avg), last 10 rewards avg %f',
+                                 self.global_step, steps_per_sec, avg, last_ten)
+                counter += n
+                self.save_vars()
         finally:
             self.cleanup()
 

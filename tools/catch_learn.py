@@ -42,7 +42,8 @@ def bar(lives, max_balls, episodes=100, seed=0):
     return 0.5 * (random_policy_mean(episodes, lives, max_balls, seed) + max_balls)
 
 
-def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampling='device', max_rep=0, nb=1):
+def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampling='device', max_rep=0, nb=1,
+                 iteration_graph=False, drain_every=None):
     import train as cli
     from manette_amd.exploration_policy import ExplorationPolicy
     from manette_amd.paac import PAACLearner
@@ -51,6 +52,7 @@ def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampli
     a.runner, a.sampling, a.seed = 'device', sampling, seed
     a.max_repetition, a.nb_choices = max_rep, nb
     a.catch_lives, a.catch_max_balls = lives, max_balls
+    a.iteration_graph, a.drain_every = iteration_graph, drain_every
     a.initial_lr, a.lr_annealing_steps = 0.02, 300000000  # pretrained/catcher/args.json
     a.debugging_folder = folder + '/'
     a.max_global_steps = 1 << 40
@@ -70,6 +72,8 @@ def train_until(L, target, max_updates, every=0, window=100):
         L.book.new_update()
         L.rollout()
         L.update()
+        if L.iteration_graph:  # (the bar is checked after every update: one drain each)
+            L.drain()
         tr = L.book.total_rewards
         mean = float(np.mean(tr[-window:])) if len(tr) >= window else None
         if every and u % every == 0:
@@ -88,18 +92,22 @@ def main():
     ap.add_argument('--ec', type=int, default=32)
     ap.add_argument('--lives', type=int, default=3)
     ap.add_argument('--max_balls', type=int, default=20)
+    ap.add_argument('--iteration_graph', action='store_true', help='train under --iteration_graph (drained after '
+                    'every update, the bar being checked there): the arithmetic is the eager path\'s')
     args = ap.parse_args()
     import torch
     target = bar(args.lives, args.max_balls)
     for seed in args.seeds:
         with tempfile.TemporaryDirectory() as tmp:
-            L = make_learner(tmp, seed, ec=args.ec, lives=args.lives, max_balls=args.max_balls)
+            L = make_learner(tmp, seed, ec=args.ec, lives=args.lives, max_balls=args.max_balls,
+                             iteration_graph=args.iteration_graph, drain_every=1 if args.iteration_graph else None)
             t0 = time.time()
             n, reached, curve = train_until(L, target, args.max_updates, args.every)
             torch.cuda.synchronize()
             dt = time.time() - t0
             L.cleanup()
-        print(json.dumps(dict(seed=seed, bar=target, reached=reached, updates=n, seconds=round(dt, 2),
+        extra = {'iteration_graph': True} if args.iteration_graph else {}
+        print(json.dumps(dict(seed=seed, bar=target, reached=reached, updates=n, seconds=round(dt, 2), **extra,
                               env_steps=n * args.ec * 5, episodes=len(L.book.total_rewards),
                               curve=[(u, None if m is None else round(m, 2)) for u, m in curve])), flush=True)
 

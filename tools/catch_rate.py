@@ -8,7 +8,13 @@
            without a host synchronisation against the lockstep form (one after every step), the two
            alternating in one process, three rounds.
 
-  python tools/catch_rate.py [--updates 300] [--skip_kernel] [--skip_rollout]
+  graph    env-steps/s of the same learner under --iteration_graph (one replayed graph per iteration,
+           drained every --drain_every) against the asynchronous eager path, two learners alternating in
+           one process, three rounds; beside it the device time per iteration (K iterations captured as one
+           graph between device events, bench.graph_time) and the wall time per iteration: the difference
+           is the host gap that remains.
+
+  python tools/catch_rate.py [--updates 300] [--skip_kernel] [--skip_rollout] [--skip_graph]
 One JSON line per measurement.
 """
 import argparse
@@ -94,16 +100,74 @@ def rollout_rates(updates=300, rounds=3, ec=32):
                           lockstep_median=round(float(np.median([b for _, b in res]))))), flush=True)
 
 
+def graph_rates(updates=300, rounds=3, ec=32, drain_every=None, inner=8, reps=5):
+    import torch
+    import bench
+    from catch_learn import make_learner
+    with tempfile.TemporaryDirectory() as tmp:
+        Le = make_learner(os.path.join(tmp, 'eager'), 0, ec=ec)
+        Lg = make_learner(os.path.join(tmp, 'graph'), 0, ec=ec, iteration_graph=True, drain_every=drain_every)
+        T, K = Le.max_local_steps, Lg.drain_every
+
+        def eager(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                Le.book.new_update()
+                Le.rollout()
+                Le.update()
+            torch.cuda.synchronize()
+            return n * T * ec / (time.perf_counter() - t0)
+
+        def graph(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            done = 0
+            while done < n:
+                k = min(K, n - done)
+                for _ in range(k):
+                    Lg.rollout()
+                Lg.drain()
+                done += k
+            torch.cuda.synchronize()
+            return n * T * ec / (time.perf_counter() - t0)
+
+        eager(20)
+        graph(20)
+        res = []
+        for _ in range(rounds):
+            res.append((graph(updates), eager(updates)))
+        assert inner * (reps + 1) <= K, 'the timed replays must fit the ring between two drains'
+        dev_us = bench.graph_time(Lg._iteration_work, inner, reps)
+        Lg.global_step += inner * (reps + 1) * T * ec  # (the mirror follows the timed iterations)
+        Lg.drain()
+        Le.cleanup()
+        Lg.cleanup()
+    wall_us = [1e6 * T * ec / g for g, _ in res]
+    print(json.dumps(dict(what='graph', ec=ec, T=T, updates=updates, drain_every=K,
+                          graph_steps_per_s=[round(g) for g, _ in res], eager_steps_per_s=[round(e) for _, e in res],
+                          graph_median=round(float(np.median([g for g, _ in res]))),
+                          eager_median=round(float(np.median([e for _, e in res]))),
+                          graph_not_slower_in_every_round=all(g >= e for g, e in res),
+                          device_us_per_iteration=round(float(np.median(dev_us)), 1),
+                          device_us_all=[round(x, 1) for x in dev_us],
+                          wall_us_per_iteration=[round(x, 1) for x in wall_us])), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--updates', type=int, default=300)
     ap.add_argument('--skip_kernel', action='store_true')
     ap.add_argument('--skip_rollout', action='store_true')
+    ap.add_argument('--skip_graph', action='store_true')
+    ap.add_argument('--drain_every', type=int, default=None)
     args = ap.parse_args()
     if not args.skip_kernel:
         kernel_times()
     if not args.skip_rollout:
         rollout_rates(args.updates)
+    if not args.skip_graph:
+        graph_rates(args.updates, drain_every=args.drain_every)
 
 
 if __name__ == '__main__':

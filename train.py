@@ -3,7 +3,8 @@
 
 Extra flags (this build only): --runner {native,python,device}, --sampling {host,device},
 --staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native,
---catch_lives, --catch_max_balls (-g catch: the device-resident game, manette_amd/catch.py).
+--catch_lives, --catch_max_balls (-g catch: the device-resident game, manette_amd/catch.py),
+--iteration_graph, --drain_every (the device game's whole iteration as one replayed graph).
 Multi-GPU: launch one process per GPU with torch.distributed.run; each rank trains
 -ec emulators of its own (--ec_scope rank, the default) or -ec / WORLD_SIZE of them (--ec_scope
 global: -ec 256 on 8 GPUs = 32 per GPU, BASELINE's "ec=256 sharded 8x32"); global env ids are
@@ -183,6 +184,14 @@ def get_arg_parser():
                         '(with --sampling device and the native runner) and the update as one captured graph around '
                         'the fused dropout backward (mt_dropout_returns_loss_backward); off: the Python step and the '
                         'eager update', dest='bayes_native')
+    parser.add_argument('--iteration_graph', action='store_true', help='--runner device --sampling device only (one '
+                        'process; NIPS / NATURE / PWYX): a whole training iteration (rollout, device bookkeeping '
+                        'mt_book_rollout, update) as one graph replayed per iteration, with no host synchronisation '
+                        'between drains; summaries, the log line and checkpoints land on drain boundaries',
+                        dest='iteration_graph')
+    parser.add_argument('--drain_every', default=None, type=int, help='--iteration_graph: iterations launched back to '
+                        'back between two drains of the device book (default max(1, 2048 // ec), the logging interval)',
+                        dest='drain_every')
     parser.add_argument('--seed', default=0, type=int, help='parameter init / device sampling seed', dest='seed')
     parser.add_argument('--comm', default='rccl', choices=['rccl', 'torch'], help='data-parallel gradient all-reduce: '
                         'rccl = RCCL behind the C ABI (mt_allreduce, one GPU per rank); torch = torch.distributed on '
