@@ -80,7 +80,17 @@ int mt_net_get_config(const mt_net *net, mt_net_config *cfg);
 /* Bytes of device workspace a forward/backward on `batch` rows needs. Zero-fill a workspace once
  * when it is allocated: the stacking chains keep per-env hand-off counters in it — the gray NATURE
  * chain (nature_chain_kernel) and the PWYX stacking conv1 launch, gray or RGB (stack_conv1_kernel) —
- * which every launch leaves at zero again, a launch whose bounded waits timed out included. */
+ * which every launch leaves at zero again, a launch whose bounded waits timed out included.
+ * Scratch contract (tests/test_scratch_contract_gpu.py): of a workspace — this one, and the LSTM frame
+ * store's (mt_lstm_frames_workspace_bytes), which has neither counters nor dropout state and needs no
+ * zero-fill — only those counters (mt_net_workspace_region kind 4) and the BAYESIAN dropout state (kind
+ * 7) persist between calls; of the other buffers only the once-zeroed alignment padding of `grad`
+ * (mt_loss_backward). Every other workspace word is scratch: a call reads only what it, or the call the
+ * header names as its predecessor on the same rows (a forward before its backward, steps 0 .. t-1 of an
+ * LSTM rollout), wrote, so outputs and gradients are the same bits whatever a workspace, an output or
+ * the variables' ranges of `grad` held before. All of it is fp32 except the max-pool argmax bytes (kind
+ * 1), the counters, the dropout mask bytes (kind 5) and the dropout state. No call writes outside the
+ * sizes reported here, or past the rows of an output it was given. */
 int mt_net_workspace_bytes(const mt_net *net, int batch, size_t *bytes);
 /* Diagnostics / parity: where a workspace keeps a forward value the backward branches on — kind 0:
  * conv layer `layer`'s stored output, post-activation ([rows][OH][OW][COUT] fp32; a pooled layer's

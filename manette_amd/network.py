@@ -155,6 +155,15 @@ class DeviceNetwork(object):
             self._ws[key] = ws
         return ws
 
+    def adopt_workspace(self, key, tensor):
+        """Use `tensor` (uint8, on this device, at least the size the call will need — workspace() and
+        lstm_workspace() replace a cached buffer that is too small) as the workspace cached under `key`:
+        workspace(batch, key)'s key, or ('lstm_frames', E, T) for the frame store's. The caller owns its
+        contents: zero-fill it once, as the hand-off counters require."""
+        assert tensor.dtype == torch.uint8 and tensor.dim() == 1 and tensor.device == self.params.device
+        self._ws[key] = tensor
+        return tensor
+
     def outputs(self, batch, key=None):
         k = (batch, key)
         o = self._out.get(k)
