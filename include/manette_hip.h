@@ -718,6 +718,88 @@ int mt_catch_step_host(const mt_catch_config *cfg, uint64_t seed, uint64_t globa
                        uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out,
                        float *over_out);
 
+/* ---- Bricks: a second device-resident environment (four actions, a brick wall) ----------------
+ * A Breakout-like game beside Catch, through the same interface: the state in HBM, one kernel per
+ * macro-step that steps, renders and stacks. (`-g breakout` stays the synthetic Atari stand-in.) Integer
+ * arithmetic only, so the kernel, the host restatement (mt_bricks_*_host) and a numpy restatement agree
+ * bit for bit. The rule:
+ *
+ *   field      84 x 84, background 0, x to the right, y down.
+ *   wall       6 rows x 14 columns of bricks, each 6 wide and 3 high, filling rows 16..33 and all 84
+ *              columns: brick (row r, column c) covers pixels x in [6c, 6c + 6), y in [16 + 3r, 19 + 3r) and
+ *              is bit k = 14 r + c of an 84-bit bitmap, stored as bricks_lo (bits 0..63) and bricks_hi
+ *              (bits 64..83; its bits 20..31 stay 0).
+ *   paddle     16 wide, 3 high, rows 79..81, its left edge paddle_x in [0, 68].
+ *   ball       2 x 2, its top-left corner (ball_x, ball_y), ball_x in [0, 82].
+ *   colours    gray: brick row r = 90 + 20 r, paddle 160, ball 255. RGB: ball (255, 64, 64), paddle
+ *              (64, 255, 64), brick rows 0..5 (200,72,72), (198,108,58), (180,122,48), (162,162,42),
+ *              (72,160,72), (66,72,200). One RENDER draws the paddle, the bricks over it, the ball over both
+ *              (a pixel takes the colour of the topmost sprite that covers it). Channel order is Catch's.
+ *   actions    0 = noop, 1 = fire, 2 = right, 3 = left (num_actions = 4, ALE Breakout's minimal set).
+ *   parked     ball_dy == 0 means the ball is parked on the paddle: the state then holds ball_dx = 0,
+ *              ball_x = paddle_x + 7 and ball_y = 77 (it is drawn there and follows the paddle).
+ *   serve      decided at the start of a next(a), if the ball is parked: if a == 1 or wait >= serve_wait:
+ *              h = mix64(seed ^ mix64((global_env << 40) ^ serve_counter) ^ 0xB41C5B0117A11E75);
+ *              serve_counter += 1; ball_x = paddle_x + 7, ball_y = 36, ball_dy = +2,
+ *              ball_dx = (-2, -1, +1, +2)[(h >> 32) & 3] (wait is left as it is); otherwise wait += 1.
+ *              serve_counter is per env and is not reset by a new game (as Catch's ball_counter).
+ *   sub-frame  1. paddle_x += (a == 2 ? +3 : a == 3 ? -3 : 0), clamped to [0, 68];
+ *              2. if the ball is parked: ball_x = paddle_x + 7 and the sub-frame ends here;
+ *              3. ball_x += ball_dx; ball_x < 0: ball_x = -ball_x, ball_dx = -ball_dx;
+ *                 ball_x > 82: ball_x = 164 - ball_x, ball_dx = -ball_dx;
+ *              4. ball_y += ball_dy; ball_y < 0: ball_y = -ball_y, ball_dy = -ball_dy;
+ *              5. brick test at the ball's leading corner cy = ball_y + (ball_dy > 0), cx = ball_x +
+ *                 (ball_dx > 0): if 16 <= cy < 34 and bit 14 ((cy - 16) / 3) + cx / 6 is set: clear it,
+ *                 reward += 1, ball_dy = -ball_dy; if the bitmap is now empty all 84 bits are set again;
+ *              6. paddle test, if ball_dy > 0 and ball_y + 1 >= 79, with off = ball_x + 1 - paddle_x:
+ *                 0 <= off <= 16: ball_dy = -2, ball_y = 77, ball_dx = (-2, -1, +1, +2)[min(3, 4 off / 17)];
+ *                 otherwise lives -= 1; at lives == 0 the episode is over (the ball stays where it is);
+ *                 with lives left the ball parks (ball_dy = ball_dx = 0, ball_x = paddle_x + 7, ball_y = 77)
+ *                 and wait = 0.
+ *   next(a)    the serve decision, then 4 sub-frames under action a (once the episode is over the
+ *              remaining sub-frames of that next are not played), then nexts += 1; the episode is also over
+ *              when nexts >= max_nexts. The reward of a next is 0..4. The observation FRAME of a next is the
+ *              per-channel maximum of the two renders of the state (positions AND bitmap) after sub-frames
+ *              3 and 4, so a brick broken in sub-frame 4 is still visible in that frame.
+ *   new game   paddle_x = 34, lives = cfg.lives, nexts = wait = 0, a full wall, the ball parked. Nothing is
+ *              played: the initial stacked state is four copies of that position's render.
+ *   macro-step, stacking: Catch's, with a clamped to [0, 3]: next(a) is run tab_rep[r] + 1 times, the
+ *              rewards summed, stopping at the first episode end, after which a new game starts at once and
+ *              the state returned is its initial state (all four stack positions replaced). */
+typedef struct mt_bricks_config {
+  int32_t lives;      /* default 3 */
+  int32_t max_nexts;  /* default 500 */
+  int32_t serve_wait; /* default 4 */
+} mt_bricks_config;
+/* Per-env state, 56 bytes, 8-byte aligned, in caller-owned memory; the field order is part of the ABI. */
+typedef struct mt_bricks_state {
+  int32_t paddle_x, ball_x, ball_y, ball_dx, ball_dy, lives, nexts, wait;
+  uint64_t bricks_lo;
+  uint32_t bricks_hi;
+  uint32_t reserved; /* written as 0 */
+  uint64_t serve_counter;
+} mt_bricks_state;
+
+/* The entry points are Catch's with this game's config and state: the same argument lists, layouts
+ * (rm_out [2][T][E]; frames_out / push_count_out in mt_preprocess_resized's layout), NULL rules and
+ * clamping (a_idx to [0, 3]). MT_ERR_ARG before any launch for bad sizes (E < 1, env0 < 0, R < 1, T < 1,
+ * t outside [0, T)), depth not 1 or 3, lives or max_nexts < 1, serve_wait < 0, out == prev, out / prev /
+ * frames_out not 16-byte or state not 8-byte aligned, frames_out without push_count_out or the reverse,
+ * or a null required pointer. Capturable: no allocation, no synchronisation, no atomics. */
+int mt_bricks_reset(const mt_bricks_config *cfg, uint64_t seed, int env0, int E, int depth, mt_bricks_state *state,
+                    uint8_t *out_state0, mt_stream_t stream);
+int mt_bricks_step(const mt_bricks_config *cfg, uint64_t seed, int env0, int E, int depth, const int32_t *tab_rep,
+                   int R, const int32_t *a_idx, const int32_t *r_idx, mt_bricks_state *state, const uint8_t *prev,
+                   uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out, float *over_out,
+                   float *rm_out, int t, int T, mt_stream_t stream);
+/* The same rule for ONE env on HOST pointers; needs no GPU (NULL frame pointers: nothing is rendered). */
+int mt_bricks_reset_host(const mt_bricks_config *cfg, uint64_t seed, uint64_t global_env, int depth,
+                         mt_bricks_state *state, uint8_t *out_state0);
+int mt_bricks_step_host(const mt_bricks_config *cfg, uint64_t seed, uint64_t global_env, int depth,
+                        const int32_t *tab_rep, int R, int a, int r, mt_bricks_state *state, const uint8_t *prev,
+                        uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out,
+                        float *over_out);
+
 /* ---- Device bookkeeping of one rollout (the learner's Bookkeeper.step, paac.py:154-205, as a kernel) ----
  * Everything a rollout of a device-resident game leaves for the host (global_step, the episode records,
  * the action / repetition histogram, the learning rate of its update) computed where the rollout ran, so

@@ -70,6 +70,19 @@ class mt_catch_state(C.Structure):
                [('ball_counter', C.c_uint64)]
 
 
+class mt_bricks_config(C.Structure):
+    """Bricks (include/manette_hip.h): lives, the cap on an episode's nexts, nexts a parked ball waits."""
+    _fields_ = [('lives', C.c_int32), ('max_nexts', C.c_int32), ('serve_wait', C.c_int32)]
+
+
+class mt_bricks_state(C.Structure):
+    """Per-env Bricks state, 56 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ('paddle_x', 'ball_x', 'ball_y', 'ball_dx', 'ball_dy', 'lives', 'nexts',
+                                         'wait')] + \
+               [('bricks_lo', C.c_uint64), ('bricks_hi', C.c_uint32), ('reserved', C.c_uint32),
+                ('serve_counter', C.c_uint64)]
+
+
 class mt_book_words(C.Structure):
     """The device book's word block (include/manette_hip.h, "Device bookkeeping"), 40 bytes."""
     _fields_ = [(n, C.c_int64) for n in ('global_step', 'written', 'acked', 'nb_actions')] + \
@@ -170,6 +183,14 @@ _HIP_SIGS = {
     'mt_catch_step_host': (_I, [C.POINTER(mt_catch_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
                                 C.POINTER(mt_catch_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
                                 C.POINTER(_F)]),
+    'mt_bricks_reset': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, _I, _I, _I, _P, _P, _P]),
+    'mt_bricks_step': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _I, _I, _P]),
+    'mt_bricks_reset_host': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, C.c_uint64, _I, C.POINTER(mt_bricks_state),
+                                  _P]),
+    'mt_bricks_step_host': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
+                                 C.POINTER(mt_bricks_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
+                                 C.POINTER(_F)]),
     'mt_book_rollout': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
                              C.c_double, C.c_double, _P]),
     'mt_book_rollout_host': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,

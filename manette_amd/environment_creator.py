@@ -21,7 +21,7 @@ MINIMAL_ACTIONS = {
 
 
 # games with a device-resident environment (--runner device): the game lives in HBM, one kernel per macro-step
-DEVICE_GAMES = ('catch',)
+DEVICE_GAMES = ('catch', 'bricks')
 
 
 def has_device_env(game):
@@ -46,6 +46,16 @@ class EnvironmentCreator(object):
                                    max_balls=int(getattr(args, 'catch_max_balls', catch.DEFAULT_MAX_BALLS)))
             self.create_environment = lambda i: catch.CatchEmulator(self.rank_offset + i, **self.catch_args)
             return
+        if game == 'bricks':
+            # the second real game (manette_amd/bricks.py), through the same two faces
+            from . import bricks
+            self.num_actions = bricks.NUM_ACTIONS
+            self.bricks_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
+                                    lives=int(getattr(args, 'bricks_lives', bricks.DEFAULT_LIVES)),
+                                    max_nexts=int(getattr(args, 'bricks_max_nexts', bricks.DEFAULT_MAX_NEXTS)),
+                                    serve_wait=int(getattr(args, 'bricks_serve_wait', bricks.DEFAULT_SERVE_WAIT)))
+            self.create_environment = lambda i: bricks.BricksEmulator(self.rank_offset + i, **self.bricks_args)
+            return
         self.num_actions = MINIMAL_ACTIONS.get(game, 18)
         self.create_environment = lambda i: SyntheticEmulator(self.rank_offset + i, self.num_actions,
                                                               rgb=self.rgb)
@@ -55,6 +65,9 @@ class EnvironmentCreator(object):
         if not has_device_env(self.game):
             raise ValueError('game %r has no device environment (--runner device serves: %s)'
                              % (self.game, ', '.join(DEVICE_GAMES)))
+        if self.game == 'bricks':
+            from . import bricks
+            return bricks.BricksDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.bricks_args)
         from . import catch
         return catch.CatchDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.catch_args)
 

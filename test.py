@@ -8,8 +8,10 @@ Differences, each a fix or a missing dependency:
   * test.py:110 calls update_memory for every arch (NameError unless LSTM): done for LSTM only;
   * an emulator whose episode ended is not stepped again (ALE gives no reward after game over,
     the synthetic stand-in would keep streaming rewards);
-  * Atari games run on the synthetic emulators (ALE absent, environment_creator.py); gif output
-    needs imageio (absent): -gn is accepted and reported as unavailable.
+  * Atari games run on the synthetic emulators (ALE absent, environment_creator.py); the device-resident
+    games are played on their host faces (-g catch: CatchEmulator, -g bricks: BricksEmulator, with the run's
+    --catch_* / --bricks_* config from args.json), so a checkpoint trained under --runner device is tested
+    on the same rule; gif output needs imageio (absent): -gn is accepted and reported as unavailable.
 """
 import argparse
 import logging

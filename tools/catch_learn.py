@@ -6,6 +6,9 @@ uniform-random policy's mean return (host restatement, no rendering) and max_bal
 deterministic: counter-based draws, no float atomics. One JSON line per seed.
 
   python tools/catch_learn.py --seeds 0 1 2 --max_updates 20000
+
+--game bricks: the same for the device-resident Bricks (manette_amd/bricks.py) at its default config, the bar
+being 4 x the uniform-random policy's mean return (bricks_bar), and --max_seconds a wall-clock cap per seed.
 """
 import argparse
 import json
@@ -42,13 +45,35 @@ def bar(lives, max_balls, episodes=100, seed=0):
     return 0.5 * (random_policy_mean(episodes, lives, max_balls, seed) + max_balls)
 
 
+def bricks_random_policy_mean(episodes=100, seed=0, **cfg):
+    """Mean return of uniform-random actions over `episodes` episodes of env 0 (mt_bricks_step_host)."""
+    from manette_amd import _lib, bricks
+    c = bricks.config(**cfg)
+    st = _lib.mt_bricks_state()
+    bricks.host_reset(c, seed, 0, 1, st)
+    rs = np.random.RandomState(12345)
+    tab = np.zeros(1, np.int32)
+    rets, ret = [], 0.0
+    while len(rets) < episodes:
+        rw, over, _ = bricks.host_step(c, seed, 0, 1, tab, int(rs.randint(4)), 0, st)
+        ret += rw
+        if over:
+            rets.append(ret)
+            ret = 0.0
+    return float(np.mean(rets))
+
+
+def bricks_bar(episodes=100, seed=0, **cfg):
+    return 4.0 * bricks_random_policy_mean(episodes, seed, **cfg)
+
+
 def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampling='device', max_rep=0, nb=1,
-                 iteration_graph=False, drain_every=None):
+                 iteration_graph=False, drain_every=None, game='catch'):
     import train as cli
     from manette_amd.exploration_policy import ExplorationPolicy
     from manette_amd.paac import PAACLearner
     a = cli.get_arg_parser().parse_args([])
-    a.game, a.arch, a.emulator_counts, a.emulator_workers = 'catch', arch, ec, 0
+    a.game, a.arch, a.emulator_counts, a.emulator_workers = game, arch, ec, 0
     a.runner, a.sampling, a.seed = 'device', sampling, seed
     a.max_repetition, a.nb_choices = max_rep, nb
     a.catch_lives, a.catch_max_balls = lives, max_balls
@@ -64,11 +89,14 @@ def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampli
     return L
 
 
-def train_until(L, target, max_updates, every=0, window=100):
+def train_until(L, target, max_updates, every=0, window=100, max_seconds=None):
     """Updates until the mean return of the last `window` finished episodes >= target (checked after
     every update); returns (updates run, reached, curve [(update, mean)])."""
     curve = []
+    t0 = time.time()
     for u in range(1, max_updates + 1):
+        if max_seconds is not None and time.time() - t0 > max_seconds:
+            return u - 1, False, curve
         L.book.new_update()
         L.rollout()
         L.update()
@@ -92,21 +120,26 @@ def main():
     ap.add_argument('--ec', type=int, default=32)
     ap.add_argument('--lives', type=int, default=3)
     ap.add_argument('--max_balls', type=int, default=20)
+    ap.add_argument('--game', choices=['catch', 'bricks'], default='catch')
+    ap.add_argument('--max_seconds', type=float, default=None, help='stop a seed after this many seconds')
     ap.add_argument('--iteration_graph', action='store_true', help='train under --iteration_graph (drained after '
                     'every update, the bar being checked there): the arithmetic is the eager path\'s')
     args = ap.parse_args()
     import torch
-    target = bar(args.lives, args.max_balls)
+    bricks_game = args.game == 'bricks'
+    target = bricks_bar() if bricks_game else bar(args.lives, args.max_balls)
     for seed in args.seeds:
         with tempfile.TemporaryDirectory() as tmp:
-            L = make_learner(tmp, seed, ec=args.ec, lives=args.lives, max_balls=args.max_balls,
+            L = make_learner(tmp, seed, ec=args.ec, lives=args.lives, max_balls=args.max_balls, game=args.game,
                              iteration_graph=args.iteration_graph, drain_every=1 if args.iteration_graph else None)
             t0 = time.time()
-            n, reached, curve = train_until(L, target, args.max_updates, args.every)
+            n, reached, curve = train_until(L, target, args.max_updates, args.every, max_seconds=args.max_seconds)
             torch.cuda.synchronize()
             dt = time.time() - t0
             L.cleanup()
         extra = {'iteration_graph': True} if args.iteration_graph else {}
+        if bricks_game:
+            extra['game'] = 'bricks'
         print(json.dumps(dict(seed=seed, bar=target, reached=reached, updates=n, seconds=round(dt, 2), **extra,
                               env_steps=n * args.ec * 5, episodes=len(L.book.total_rewards),
                               curve=[(u, None if m is None else round(m, 2)) for u, m in curve])), flush=True)

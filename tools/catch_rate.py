@@ -14,8 +14,9 @@
            graph between device events, bench.graph_time) and the wall time per iteration: the difference
            is the host gap that remains.
 
-  python tools/catch_rate.py [--updates 300] [--skip_kernel] [--skip_rollout] [--skip_graph]
-One JSON line per measurement.
+  python tools/catch_rate.py [--updates 300] [--skip_kernel] [--skip_rollout] [--skip_graph] [--game bricks]
+One JSON line per measurement. --game bricks measures the device-resident Bricks (manette_amd/bricks.py) the
+same way: its kernel lines carry bricks_step_us beside catch_step_us and preprocess_resized_us of the same run.
 """
 import argparse
 import json
@@ -31,10 +32,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 
-def kernel_times(inner=50, reps=5):
+def _tag(game):
+    return {} if game == 'catch' else {'game': game}  # (the default's lines are what they were)
+
+
+def kernel_times(inner=50, reps=5, game='catch'):
     import torch
     import bench
-    from manette_amd import catch, network as devnet
+    from manette_amd import bricks, catch, network as devnet
     for E in (32, 64):
         for depth in (1, 3):
             for R in (1, 11):
@@ -63,6 +68,26 @@ def kernel_times(inner=50, reps=5):
 
                 t_env = bench.graph_time(step, inner, reps)
                 t_stack = bench.graph_time(stack, inner, reps)
+                if game == 'bricks':  # the same buffers, indices and table under the other game (a in 0..3)
+                    bdev = bricks.BricksDevice(E, tab, seed=1, rgb=depth == 3)
+                    ab = torch.from_numpy(rs.randint(0, 4, E).astype(np.int32)).cuda()
+                    bdev.reset(bufs[0])
+                    for _ in range(8):  # (balls in play: the first nexts serve)
+                        bdev.step(ab, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)
+
+                    def bstep():
+                        bdev.step(ab, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
+                        k[0] += 1
+
+                    t_b = bench.graph_time(bstep, inner, reps)
+                    print(json.dumps(dict(what='kernel', game='bricks', E=E, depth=depth, R=R,
+                                          bricks_step_us=round(float(np.median(t_b)), 2),
+                                          catch_step_us=round(float(np.median(t_env)), 2),
+                                          preprocess_resized_us=round(float(np.median(t_stack)), 2),
+                                          bricks_step_all=[round(x, 2) for x in t_b],
+                                          catch_step_all=[round(x, 2) for x in t_env],
+                                          preprocess_resized_all=[round(x, 2) for x in t_stack])), flush=True)
+                    continue
                 print(json.dumps(dict(what='kernel', E=E, depth=depth, R=R, mean_pushes=float(count.float().mean()),
                                       catch_step_us=round(float(np.median(t_env)), 2),
                                       preprocess_resized_us=round(float(np.median(t_stack)), 2),
@@ -70,11 +95,11 @@ def kernel_times(inner=50, reps=5):
                                       preprocess_resized_all=[round(x, 2) for x in t_stack])), flush=True)
 
 
-def rollout_rates(updates=300, rounds=3, ec=32):
+def rollout_rates(updates=300, rounds=3, ec=32, game='catch'):
     import torch
     from catch_learn import make_learner
     with tempfile.TemporaryDirectory() as tmp:
-        L = make_learner(tmp, 0, ec=ec)
+        L = make_learner(tmp, 0, ec=ec, game=game)
         T = L.max_local_steps
 
         def run(lockstep, n):
@@ -94,19 +119,19 @@ def rollout_rates(updates=300, rounds=3, ec=32):
         for _ in range(rounds):
             res.append((run(False, updates), run(True, updates)))
         L.cleanup()
-    print(json.dumps(dict(what='rollout', ec=ec, T=T, updates=updates,
+    print(json.dumps(dict(what='rollout', **_tag(game), ec=ec, T=T, updates=updates,
                           async_steps_per_s=[round(a) for a, _ in res], lockstep_steps_per_s=[round(b) for _, b in res],
                           async_median=round(float(np.median([a for a, _ in res]))),
                           lockstep_median=round(float(np.median([b for _, b in res]))))), flush=True)
 
 
-def graph_rates(updates=300, rounds=3, ec=32, drain_every=None, inner=8, reps=5):
+def graph_rates(updates=300, rounds=3, ec=32, drain_every=None, inner=8, reps=5, game='catch'):
     import torch
     import bench
     from catch_learn import make_learner
     with tempfile.TemporaryDirectory() as tmp:
-        Le = make_learner(os.path.join(tmp, 'eager'), 0, ec=ec)
-        Lg = make_learner(os.path.join(tmp, 'graph'), 0, ec=ec, iteration_graph=True, drain_every=drain_every)
+        Le = make_learner(os.path.join(tmp, 'eager'), 0, ec=ec, game=game)
+        Lg = make_learner(os.path.join(tmp, 'graph'), 0, ec=ec, iteration_graph=True, drain_every=drain_every, game=game)
         T, K = Le.max_local_steps, Lg.drain_every
 
         def eager(n):
@@ -144,7 +169,7 @@ def graph_rates(updates=300, rounds=3, ec=32, drain_every=None, inner=8, reps=5)
         Le.cleanup()
         Lg.cleanup()
     wall_us = [1e6 * T * ec / g for g, _ in res]
-    print(json.dumps(dict(what='graph', ec=ec, T=T, updates=updates, drain_every=K,
+    print(json.dumps(dict(what='graph', **_tag(game), ec=ec, T=T, updates=updates, drain_every=K,
                           graph_steps_per_s=[round(g) for g, _ in res], eager_steps_per_s=[round(e) for _, e in res],
                           graph_median=round(float(np.median([g for g, _ in res]))),
                           eager_median=round(float(np.median([e for _, e in res]))),
@@ -161,13 +186,14 @@ def main():
     ap.add_argument('--skip_rollout', action='store_true')
     ap.add_argument('--skip_graph', action='store_true')
     ap.add_argument('--drain_every', type=int, default=None)
+    ap.add_argument('--game', choices=['catch', 'bricks'], default='catch')
     args = ap.parse_args()
     if not args.skip_kernel:
-        kernel_times()
+        kernel_times(game=args.game)
     if not args.skip_rollout:
-        rollout_rates(args.updates)
+        rollout_rates(args.updates, game=args.game)
     if not args.skip_graph:
-        graph_rates(args.updates, drain_every=args.drain_every)
+        graph_rates(args.updates, drain_every=args.drain_every, game=args.game)
 
 
 if __name__ == '__main__':

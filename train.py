@@ -4,6 +4,7 @@
 Extra flags (this build only): --runner {native,python,device}, --sampling {host,device},
 --staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native,
 --catch_lives, --catch_max_balls (-g catch: the device-resident game, manette_amd/catch.py),
+--bricks_lives, --bricks_max_nexts, --bricks_serve_wait (-g bricks: the second one, manette_amd/bricks.py),
 --iteration_graph, --drain_every (the device game's whole iteration as one replayed graph).
 Multi-GPU: launch one process per GPU with torch.distributed.run; each rank trains
 -ec emulators of its own (--ec_scope rank, the default) or -ec / WORLD_SIZE of them (--ec_scope
@@ -166,9 +167,12 @@ def get_arg_parser():
     parser.add_argument('--activation', default='relu', type=str, help="activation function for the network", dest="activation")
     parser.add_argument('--alpha_leaky_relu', default=0.1, type=float, help="coef for leaky relu", dest="alpha_leaky_relu")
     # this build
-    parser.add_argument('--runner', default='native', choices=['native', 'python', 'device'], help='native: C++ emulator threads + GPU preprocess; python: reference-contract emulator processes; device: the game lives in HBM, one kernel per macro-step steps, renders and stacks it (-g catch; not --arch LSTM)', dest='runner')
+    parser.add_argument('--runner', default='native', choices=['native', 'python', 'device'], help='native: C++ emulator threads + GPU preprocess; python: reference-contract emulator processes; device: the game lives in HBM, one kernel per macro-step steps, renders and stacks it (-g catch or -g bricks; not --arch LSTM)', dest='runner')
     parser.add_argument('--catch_lives', default=3, type=int, help='-g catch: misses that end an episode', dest='catch_lives')
     parser.add_argument('--catch_max_balls', default=20, type=int, help='-g catch: balls of an episode', dest='catch_max_balls')
+    parser.add_argument('--bricks_lives', default=3, type=int, help='-g bricks: lost balls that end an episode', dest='bricks_lives')
+    parser.add_argument('--bricks_max_nexts', default=500, type=int, help='-g bricks: the cap on an episode\'s emulator steps (next() calls)', dest='bricks_max_nexts')
+    parser.add_argument('--bricks_serve_wait', default=4, type=int, help='-g bricks: emulator steps a parked ball waits for a fire action before it is served anyway', dest='bricks_serve_wait')
     parser.add_argument('--staging', default='resized', choices=['in_place', 'zero_copy', 'copy', 'pooled', 'resized'],
                         help='native runner screens: each push\'s final 84x84 frame pooled + resized by the emulator '
                              'threads and read in place from pinned memory (resized), the GPU reading the emulators\' '
