@@ -859,6 +859,65 @@ int mt_book_rollout_host(const mt_book_state *book, const int32_t *a_idx, const 
                          const float *over, const int32_t *tab_rep, int A, int R, int E, int T, int64_t env_offset,
                          int64_t envs_total, double initial_lr, double lr_annealing_steps);
 
+/* ---- Device evaluation (K episodes on each of N envs of a device-resident game) ----------------------
+ * The env kernels restart a game the moment it ends, so a fixed amount of play ("K episodes on every
+ * env") needs somebody to keep the per-episode results and to stop counting an env after its K-th
+ * episode. These three kernels do, in device memory: the host enqueues macro-steps (forward, draw, env
+ * kernel, mt_eval_step) and reads the word block once per block of steps. The rules:
+ *
+ *   reset      ret_acc, len_acc, done, returns and lengths are zeroed; remaining = N * K; steps = 0.
+ *   step       once after each env kernel, on that kernel's reward_out (the unclipped sum) and over_out.
+ *              For env e with done[e] < K:
+ *                1. ret_acc[e] += reward[e] (one fp32 add);
+ *                2. len_acc[e] += clamp(tab_rep[clamp(r_idx[e], 0, R - 1)], 0, 255) + 1: the planned nexts
+ *                   that Bookkeeper counts, under the env kernels' clamps;
+ *                3. where over[e] != 0: returns[e][done[e]] = ret_acc[e], lengths[e][done[e]] = len_acc[e],
+ *                   done[e] += 1, both accumulators zeroed.
+ *              An env with done[e] == K is frozen: the env kernel still steps it and nothing of it is
+ *              recorded. Then remaining = the sum over e of K - done[e] (an integer sum: per-thread
+ *              partials combined through LDS) and steps += 1.
+ *   summarize  over the finished entries, flat index i = e * K + k counted iff k < done[e]. Lane j of 256
+ *              takes i = j, j + 256, ... in ascending order; the 256 partials are then combined by the
+ *              tree part[j] (+)= part[j + s] for s = 128, 64, ..., 1, lane j on the left. sum and sumsq
+ *              are doubles of (double)returns[i], the square rounded to double before it is added (no
+ *              fused multiply-add); min and max are fp32 (a < b ? a : b, the earlier partial first);
+ *              length_sum and episodes are int64; unfinished = remaining. With no finished episode every
+ *              field but unfinished is 0. The host restatement reduces in the same order, so the two agree
+ *              bit for bit.
+ *
+ * One workgroup of 256 per call; no atomics; allocates nothing, does not synchronise, capturable. Every
+ * pointer is device memory (mt_eval_*) or host memory (mt_eval_*_host, the same rules with no GPU; the
+ * kernels are pinned against them). r_idx: [N] int32; reward, over: [N] fp32; tab_rep: [R] int32.
+ * MT_ERR_ARG before any launch for a null pointer, N, K or R < 1, N * K > 2^30, or an int64 / double
+ * buffer (len_acc, lengths, words, the summary) that is not 8-byte aligned. */
+typedef struct mt_eval_words {
+  int64_t remaining; /* episodes still owed: the sum of K - done[e] */
+  int64_t steps;     /* mt_eval_step calls since the reset */
+} mt_eval_words;
+typedef struct mt_eval_state {
+  float *ret_acc;   /* [N] */
+  int64_t *len_acc; /* [N] */
+  int32_t *done;    /* [N] */
+  float *returns;   /* [N][K] */
+  int64_t *lengths; /* [N][K] */
+  mt_eval_words *words;
+  int32_t N, K;
+} mt_eval_state;
+typedef struct mt_eval_summary {
+  int64_t episodes, unfinished, length_sum;
+  double sum, sumsq;
+  float min, max;
+  int32_t pad[2]; /* written as 0 */
+} mt_eval_summary;
+int mt_eval_reset(const mt_eval_state *state, mt_stream_t stream);
+int mt_eval_step(const mt_eval_state *state, const int32_t *r_idx, const float *reward, const float *over,
+                 const int32_t *tab_rep, int R, mt_stream_t stream);
+int mt_eval_summarize(const mt_eval_state *state, mt_eval_summary *out, mt_stream_t stream);
+int mt_eval_reset_host(const mt_eval_state *state);
+int mt_eval_step_host(const mt_eval_state *state, const int32_t *r_idx, const float *reward, const float *over,
+                      const int32_t *tab_rep, int R);
+int mt_eval_summarize_host(const mt_eval_state *state, mt_eval_summary *out);
+
 #ifdef __cplusplus
 }
 #endif

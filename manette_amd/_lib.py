@@ -99,6 +99,23 @@ class mt_book_state(C.Structure):
                [('capacity', C.c_int64)]
 
 
+class mt_eval_words(C.Structure):
+    """The device evaluation's word block (include/manette_hip.h, "Device evaluation"), 16 bytes."""
+    _fields_ = [('remaining', C.c_int64), ('steps', C.c_int64)]
+
+
+class mt_eval_state(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('ret_acc', 'len_acc', 'done', 'returns', 'lengths', 'words')] + \
+               [('N', C.c_int32), ('K', C.c_int32)]
+
+
+class mt_eval_summary(C.Structure):
+    """What mt_eval_summarize writes, 56 bytes."""
+    _fields_ = [(n, C.c_int64) for n in ('episodes', 'unfinished', 'length_sum')] + \
+               [('sum', C.c_double), ('sumsq', C.c_double), ('min', C.c_float), ('max', C.c_float),
+                ('pad', C.c_int32 * 2)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -195,6 +212,12 @@ _HIP_SIGS = {
                              C.c_double, C.c_double, _P]),
     'mt_book_rollout_host': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
                                   C.c_double, C.c_double]),
+    'mt_eval_reset': (_I, [C.POINTER(mt_eval_state), _P]),
+    'mt_eval_step': (_I, [C.POINTER(mt_eval_state), _P, _P, _P, _P, _I, _P]),
+    'mt_eval_summarize': (_I, [C.POINTER(mt_eval_state), _P, _P]),
+    'mt_eval_reset_host': (_I, [C.POINTER(mt_eval_state)]),
+    'mt_eval_step_host': (_I, [C.POINTER(mt_eval_state), _P, _P, _P, _P, _I]),
+    'mt_eval_summarize_host': (_I, [C.POINTER(mt_eval_state), _P]),
 }
 
 _HOST_SIGS = {

@@ -32,6 +32,12 @@ def config(lives=DEFAULT_LIVES, max_nexts=DEFAULT_MAX_NEXTS, serve_wait=DEFAULT_
     return _lib.mt_bricks_config(int(lives), int(max_nexts), int(serve_wait))
 
 
+def max_episode_nexts(cfg):
+    """An upper bound on the next() calls of one episode (so on its macro-steps, each of which plays at
+    least one): the rule ends an episode when nexts >= max_nexts."""
+    return int(cfg.max_nexts)
+
+
 def host_reset(cfg, seed, global_env, depth, state, out=None):
     """A new game into `state` (serve_counter = 0); out (84, 84, 4*depth) uint8 or None."""
     _lib.check(_lib.hip().mt_bricks_reset_host(C.byref(cfg), C.c_uint64(seed), C.c_uint64(global_env), depth,

@@ -25,6 +25,14 @@ def config(lives=DEFAULT_LIVES, max_balls=DEFAULT_MAX_BALLS):
     return _lib.mt_catch_config(int(lives), int(max_balls))
 
 
+def max_episode_nexts(cfg):
+    """An upper bound on the next() calls of one episode (so on its macro-steps, each of which plays at
+    least one): an episode sees at most max_balls balls, a ball needs 38 sub-frames from its spawn to
+    the paddle row (the rule, "next(a)") and the following ball spawns in the sub-frame that settled the
+    last, so an episode has at most 38 * max_balls sub-frames, four to a next."""
+    return (38 * int(cfg.max_balls) + 3) // 4
+
+
 def host_reset(cfg, seed, global_env, depth, state, out=None):
     """A new game (ball_counter = 0) into `state`; out (84, 84, 4*depth) uint8 or None."""
     _lib.check(_lib.hip().mt_catch_reset_host(C.byref(cfg), C.c_uint64(seed), C.c_uint64(global_env), depth,

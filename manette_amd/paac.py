@@ -245,6 +245,16 @@ class PAACLearner(ActorLearner):
         self._buckets = None  # data parallel: flat offset splitting the two all-reduce buckets
         self.summaries = None  # TensorBoard event files of the chief (manette_amd/summary.py)
         self._logged_episodes = 0
+        # --eval_every: the chief plays eval_envs x eval_episodes fixed games in device memory with the
+        # learner's own parameter buffer (manette_amd/evaluate.py); nothing writable is shared with training
+        self.eval_every = int(getattr(args, 'eval_every', 0) or 0)
+        self.eval_envs = int(getattr(args, 'eval_envs', 64))
+        self.eval_episodes = int(getattr(args, 'eval_episodes', 1))
+        self.eval_greedy = bool(getattr(args, 'eval_greedy', False))
+        self._eval_policy_args = args
+        self.eval_history = []  # (global_step, EvalResult)
+        self._evaluator = None
+        self._last_eval_step = None
 
     # ------------------------------------------------------------------------------------------
     def _plan_threads(self):
@@ -1042,6 +1052,44 @@ class PAACLearner(ActorLearner):
             self.summaries.log_values(self._union_steps, 'steps_per_episode', self.global_step, timestep=1)
         self.summaries.flush()
 
+    def evaluate(self):
+        """One device-resident evaluation of the current parameters (chief only): the scalars eval/* at
+        global_step, one log line, an entry of eval_history. Every evaluation of a run plays the same games
+        under the same draw stream, so two of them differ by the parameters alone."""
+        if not self.is_chief:
+            return None
+        from . import evaluate
+        if self._evaluator is None:
+            policy = evaluate.policy_from_args(self._eval_policy_args, greedy=self.eval_greedy,
+                                               rows_per_call=self.eval_envs)
+            self._evaluator = evaluate.DeviceEvaluator(
+                self.network, self.environment_creator, self.tab_rep, self.eval_envs, episodes=self.eval_episodes,
+                policy=policy, draw_seed=self.sample_seed ^ evaluate.EVAL_SEED_SALT, env0=evaluate.EVAL_ENV0)
+        res = self._evaluator.run()
+        self._last_eval_step = self.global_step
+        self.eval_history.append((self.global_step, res))
+        if self.summaries is None:
+            from .summary import LearnerSummaries
+            self.summaries = LearnerSummaries(self.debugging_folder)
+            self._union_rewards, self._union_steps, self._summary_step = [], [], self.global_step_start
+        self.summaries.evaluation(self.global_step, res)
+        self.summaries.flush()
+        logging.info('Evaluation at step %d: %d episodes (%d unfinished), return mean %f min %f max %f std %f, '
+                     'mean length %f', self.global_step, res.episodes, res.unfinished, res.mean, res.min, res.max,
+                     res.std, res.mean_length)
+        return res
+
+    def _maybe_evaluate(self, before, final=False):
+        """--eval_every S: evaluate when global_step crossed a multiple of S since `before`; final: once
+        at the end of train(), unless the last evaluation already saw these parameters."""
+        if self.eval_every <= 0:
+            return
+        if final:
+            if self._last_eval_step != self.global_step:
+                self.evaluate()
+        elif self.global_step // self.eval_every > before // self.eval_every:
+            self.evaluate()
+
     def train(self):
         """Main actor learner loop (paac.py:86-297)."""
         self.start()
@@ -1053,6 +1101,7 @@ class PAACLearner(ActorLearner):
         try:
             while self.global_step < self.max_global_steps:
                 loop_start_time = time.time()
+                step_before = self.global_step
                 self.book.new_update()
                 if counter == 0 and self.world > 1:  # the first all-reduce, bounded (comm.Deadline)
                     from . import comm
@@ -1064,6 +1113,7 @@ class PAACLearner(ActorLearner):
                     self.rollout()
                     self.update()
                 self.write_summaries()
+                self._maybe_evaluate(step_before)
                 counter += 1
                 if counter % max(1, 2048 // self.emulator_counts) == 0:
                     torch.cuda.synchronize()
@@ -1077,6 +1127,7 @@ class PAACLearner(ActorLearner):
                 self.save_vars()
             if self.world > 1:  # (every rank: a collective) the episodes since the last gather
                 self._write_summaries_dp(final=True)
+            self._maybe_evaluate(self.global_step, final=True)
         finally:
             self.cleanup()
 
@@ -1090,11 +1141,13 @@ class PAACLearner(ActorLearner):
         try:
             while self.global_step < self.max_global_steps:
                 loop_start_time = time.time()
+                step_before = self.global_step
                 n = min(self.drain_every, -(-(self.max_global_steps - self.global_step) // per))
                 for _ in range(n):
                     self._iteration()
                 self.drain()
                 self.write_summaries()
+                self._maybe_evaluate(step_before)
                 if (counter + n) // log_every > counter // log_every:
                     now = time.time()
                     tr = self.book.total_rewards
@@ -1105,6 +1158,7 @@ class PAACLearner(ActorLearner):
                                  self.global_step, steps_per_sec, avg, last_ten)
                 counter += n
                 self.save_vars()
+            self._maybe_evaluate(self.global_step, final=True)
         finally:
             self.cleanup()
 
@@ -1112,6 +1166,9 @@ class PAACLearner(ActorLearner):
         try:
             torch.cuda.synchronize()
             self._destroy_graphs()
+            if self._evaluator is not None:
+                self._evaluator.close()
+                self._evaluator = None
             super(PAACLearner, self).cleanup()
         finally:
             if self.native_step is not None:

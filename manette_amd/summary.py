@@ -77,6 +77,9 @@ class EventWriter(object):
             self._f = None
 
 
+EVAL_TAGS = ('eval/mean_return', 'eval/min_return', 'eval/max_return', 'eval/std_return', 'eval/mean_length')
+
+
 class LearnerSummaries(object):
     """The reference's summary calls (paac.py:23-31, :65-77, :191-199, :265-266) on an EventWriter."""
 
@@ -103,6 +106,12 @@ class LearnerSummaries(object):
             self.writer.add_scalars(global_step, [(tag + '/mean', mean), (tag + '/min', min(last)),
                                                   (tag + '/max', max(last)), (tag + '/std', std),
                                                   (tag + '/std_over_mean', ratio)])
+
+    def evaluation(self, global_step, result):
+        """The scalars of one device-resident evaluation (manette_amd/evaluate.py; this build only)."""
+        self.writer.add_scalars(global_step, [(EVAL_TAGS[0], result.mean), (EVAL_TAGS[1], result.min),
+                                              (EVAL_TAGS[2], result.max), (EVAL_TAGS[3], result.std),
+                                              (EVAL_TAGS[4], result.mean_length)])
 
     def flush(self):
         self.writer.flush()

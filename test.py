@@ -11,7 +11,14 @@ Differences, each a fix or a missing dependency:
   * Atari games run on the synthetic emulators (ALE absent, environment_creator.py); the device-resident
     games are played on their host faces (-g catch: CatchEmulator, -g bricks: BricksEmulator, with the run's
     --catch_* / --bricks_* config from args.json), so a checkpoint trained under --runner device is tested
-    on the same rule; gif output needs imageio (absent): -gn is accepted and reported as unavailable.
+    on the same rule; gif output needs imageio (absent): -gn is accepted and reported as unavailable;
+  * --runner device (this build; the default `host` is the loop above, untouched): the device-resident
+    games are played where they live, -tc envs (global ids 0..tc-1, the host face's) times -ep episodes
+    each, by manette_amd.evaluate.DeviceEvaluator: forward, draw, env kernel and the per-episode
+    bookkeeping (mt_eval_step) enqueued with one host look per block of macro-steps. --greedy picks the
+    argmax chooser (else the one args.json implies: multinomial or its e-greedy settings), --draw_seed
+    fixes the draw stream (default: from the clock, as the host loop's). -np is not applied there: the
+    games randomise through their own ball / serve streams.
 """
 import argparse
 import logging
@@ -47,7 +54,48 @@ def get_arg_parser():
                         dest="gif_folder")
     parser.add_argument('-d', '--device', default='/gpu:0', type=str,
                         help="Device to be used ('/cpu:0', '/gpu:0', '/gpu:1',...)", dest="device")
+    # this build
+    parser.add_argument('--runner', default='host', choices=['host', 'device'],
+                        help="host: the reference's loop on the emulators' host faces; device: a device-resident game "
+                             "(-g catch, -g bricks) evaluated in HBM (manette_amd/evaluate.py)", dest='test_runner')
+    parser.add_argument('--greedy', action='store_true', help='--runner device: the argmax chooser (default: the one '
+                        'the run\'s args.json implies)', dest='greedy')
+    parser.add_argument('--draw_seed', default=None, type=int, help='--runner device: seed of the draw stream '
+                        '(default: from the clock)', dest='draw_seed')
+    parser.add_argument('-ep', '--episodes_per_env', default=1, type=int, help='--runner device: episodes played on '
+                        'each of the -tc envs', dest='episodes_per_env')
     return parser
+
+
+def print_summary(n, game, rewards):
+    print('Performed {} tests for {}.'.format(n, game))
+    print('Mean: {0:.2f}'.format(np.mean(rewards)))
+    print('Min: {0:.2f}'.format(np.min(rewards)))
+    print('Max: {0:.2f}'.format(np.max(rewards)))
+    print('Std: {0:.2f}'.format(np.std(rewards)))
+
+
+def run_device(args, network, env_creator, explo_policy, max_macro_steps=None):
+    """--runner device: -tc envs x -ep episodes in device memory; returns the per-episode rewards."""
+    from manette_amd import evaluate
+    if args.noops != 0:
+        logging.warning('-np is not applied under --runner device: the device games randomise through their own '
+                        'ball / serve streams')
+    seed = int(time.time()) if args.draw_seed is None else int(args.draw_seed)
+    policy = evaluate.policy_from_args(args, greedy=args.greedy, rows_per_call=args.test_count)
+    ev = evaluate.DeviceEvaluator(network, env_creator, explo_policy.tab_rep, args.test_count,
+                                  episodes=args.episodes_per_env, policy=policy, draw_seed=seed, env0=0,
+                                  max_macro_steps=max_macro_steps)
+    try:
+        res = ev.run()
+    finally:
+        ev.close()
+    if res.unfinished:
+        logging.warning('%d episodes did not finish within %d macro-steps', res.unfinished, res.macro_steps)
+    rewards = res.finished()
+    # (nothing finished under a max_macro_steps cap: the summary lines of a single 0, as the host loop's zeros)
+    print_summary(res.episodes, args.game, rewards if rewards.size else np.zeros(1, np.float32))
+    return rewards
 
 
 def run(args, max_macro_steps=None):
@@ -59,6 +107,7 @@ def run(args, max_macro_steps=None):
     from manette_amd.exploration_policy import Action, ExplorationPolicy
 
     device = args.device
+    test_runner = getattr(args, 'test_runner', 'host')
     for k, v in logger_utils.load_args(os.path.join(args.folder, 'args.json')).items():
         setattr(args, k, v)
     args.max_global_steps = 0
@@ -73,6 +122,11 @@ def run(args, max_macro_steps=None):
     rng = np.random.RandomState(int(time.time()))
     args.random_seed = rng.randint(1000)
 
+    if test_runner == 'device':
+        from manette_amd.environment_creator import DEVICE_GAMES, has_device_env
+        if not has_device_env(args.game):
+            raise ValueError('--runner device needs a game with a device environment (-g %s), got -g %s'
+                             % (' | '.join(DEVICE_GAMES), args.game))
     explo_policy = ExplorationPolicy(args, test=False)
     network_creator, env_creator = train_cli.get_network_and_environment_creator(args, explo_policy)
     network = network_creator()
@@ -86,6 +140,8 @@ def run(args, max_macro_steps=None):
         network.set_variables({k: v for k, v in t.items() if not k.endswith((SLOT_MS, SLOT_MOM))})
 
     n = args.test_count
+    if test_runner == 'device':
+        return run_device(args, network, env_creator, explo_policy, max_macro_steps)
     if args.arch == 'BAYESIAN':
         # dropout stays on in evaluation, as in the reference (no training switch, networks.py:194-204)
         network.set_dropout_state('test', int(getattr(args, 'seed', 0)), 0, batch=n)

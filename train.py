@@ -5,7 +5,8 @@ Extra flags (this build only): --runner {native,python,device}, --sampling {host
 --staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native,
 --catch_lives, --catch_max_balls (-g catch: the device-resident game, manette_amd/catch.py),
 --bricks_lives, --bricks_max_nexts, --bricks_serve_wait (-g bricks: the second one, manette_amd/bricks.py),
---iteration_graph, --drain_every (the device game's whole iteration as one replayed graph).
+--iteration_graph, --drain_every (the device game's whole iteration as one replayed graph),
+--eval_every, --eval_envs, --eval_episodes, --eval_greedy (device-resident evaluation during training).
 Multi-GPU: launch one process per GPU with torch.distributed.run; each rank trains
 -ec emulators of its own (--ec_scope rank, the default) or -ec / WORLD_SIZE of them (--ec_scope
 global: -ec 256 on 8 GPUs = 32 per GPU, BASELINE's "ec=256 sharded 8x32"); global env ids are
@@ -35,6 +36,18 @@ def validate_args(args):
     """Flag combinations that are refused, before any device allocation."""
     from manette_amd.paac import check_arch_flags
     check_arch_flags(args)
+    # --eval_*: device-resident evaluation during training (manette_amd/evaluate.py), off by default
+    every, envs, episodes = (int(getattr(args, 'eval_every', 0)), int(getattr(args, 'eval_envs', 64)),
+                             int(getattr(args, 'eval_episodes', 1)))
+    if every < 0:
+        raise ValueError('--eval_every must be >= 0 (0 = off), got %d' % every)
+    if envs < 1 or episodes < 1:
+        raise ValueError('--eval_envs and --eval_episodes must be >= 1, got %d and %d' % (envs, episodes))
+    if every > 0 or getattr(args, 'eval_greedy', False):
+        from manette_amd.environment_creator import DEVICE_GAMES, has_device_env
+        if not has_device_env(getattr(args, 'game', 'pong')):
+            raise ValueError('--eval_every / --eval_greedy evaluate in device memory and need a game with a device '
+                             'environment (-g %s), got -g %s' % (' | '.join(DEVICE_GAMES), args.game))
 
 
 def main(args):
@@ -196,6 +209,14 @@ def get_arg_parser():
     parser.add_argument('--drain_every', default=None, type=int, help='--iteration_graph: iterations launched back to '
                         'back between two drains of the device book (default max(1, 2048 // ec), the logging interval)',
                         dest='drain_every')
+    parser.add_argument('--eval_every', default=0, type=int, help='-g catch / -g bricks: every this many global steps '
+                        '(0 = off) the chief plays --eval_envs x --eval_episodes fixed games in device memory with the '
+                        'current parameters (manette_amd/evaluate.py) and writes eval/* scalars; also once at the end. '
+                        'With --iteration_graph: at the first drain at or past the multiple', dest='eval_every')
+    parser.add_argument('--eval_envs', default=64, type=int, help='--eval_every: envs of an evaluation', dest='eval_envs')
+    parser.add_argument('--eval_episodes', default=1, type=int, help='--eval_every: episodes per env', dest='eval_episodes')
+    parser.add_argument('--eval_greedy', action='store_true', help='--eval_every: evaluate the argmax policy (default: '
+                        'the training chooser)', dest='eval_greedy')
     parser.add_argument('--seed', default=0, type=int, help='parameter init / device sampling seed', dest='seed')
     parser.add_argument('--comm', default='rccl', choices=['rccl', 'torch'], help='data-parallel gradient all-reduce: '
                         'rccl = RCCL behind the C ABI (mt_allreduce, one GPU per rank); torch = torch.distributed on '
