@@ -800,6 +800,101 @@ int mt_bricks_step_host(const mt_bricks_config *cfg, uint64_t seed, uint64_t glo
                         uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out,
                         float *over_out);
 
+/* ---- Tetris: the reference's own game as a third device-resident environment (five actions) ----
+ * The rule of the reference's tetris.py (88-119, 147-170, 213-335) as tetris_emulator.py drives it, quirks
+ * included, through Bricks' interface. Integer arithmetic only; the kernel, the host restatement
+ * (mt_tetris_*_host) and a Python restatement agree field for field, and the host restatement is pinned,
+ * act by act, to recordings of the reference's own code (tests/golden/tetris_rule.npz). The rule:
+ *
+ *   board      10 columns x 22 rows, x to the right, y down; a cell holds a colour id 0..7 (0 = empty).
+ *              Row y is the word board[y], cell x its bits 3x .. 3x+2 (bits 30, 31 stay 0). Below row 21
+ *              lies a floor: every cell of a row >= 22 counts as occupied, as does a column >= 10.
+ *   shapes     ids 1..7, as matrices of cells (rows top-down), in tetris_shapes' order:
+ *              1 = 111/010, 2 = 022/220, 3 = 330/033, 4 = 400/444, 5 = 005/555, 6 = 6666, 7 = 77/77.
+ *              The falling piece is (piece, rot, x, y): shape `piece` rotated rot = 0..3 times, its matrix's
+ *              top-left cell at column x, row y. One rotation of an H x W matrix gives the W x H matrix
+ *              new[i][j] = old[j][W-1-i]; four give the first again (rot counts modulo 4). A piece COLLIDES
+ *              at (x, y) iff one of its non-zero cells lies on an occupied cell.
+ *   actions    0 = noop, 1 = left, 2 = right, 3 = manual drop, 4 = rotate (num_actions = 5).
+ *              left / right: nx = x -+ 1 clamped to [0, 10 - W]; x = nx unless the piece collides at (nx, y).
+ *              manual drop: reward += 1 (on every call, whether or not it locks), then DROP.
+ *              rotate: rot += 1 unless the rotated piece collides at (x, y) (which covers leaving the board
+ *              on the right or at the bottom).
+ *   DROP       y += 1. If the piece now collides: LOCK: its non-zero cells are written into the board at
+ *              (x, y - 1); the next piece spawns: piece = next_piece, rot = 0, x = (3, 3, 4) for W =
+ *              (3, 4, 2) (int(5 - W/2)), y = 0, next_piece = 1 + DRAW; the game is OVER iff the spawned piece
+ *              collides (tested before any row is removed, and it stays over); then every full row (no
+ *              empty cell) is removed, the rows above it moving down and empty rows entering at the top;
+ *              with n the number of removed rows (n <= 4; the index is clamped): lines += n, reward +=
+ *              (0, 40, 100, 300, 1200)[n] x level; then, if lines >= 6 level: level += 1 (once per lock)
+ *              and speed = max(1, speed - 1).
+ *   act(a)     the action; then, if speed_counter % speed == 0 and the game is not over, one DROP without
+ *              the point (gravity: also when the action has just locked a piece and spawned the next);
+ *              then speed_counter += 1.
+ *   next(a)    act(a); nexts += 1; the episode is over iff the game is over or nexts >= max_nexts (the cap
+ *              is this project's: an episode that keeps clearing rows is otherwise unbounded). The reward
+ *              of a next is its score difference. The observation FRAME of a next is ONE render of the
+ *              state after the act (the reference draws before the action and takes the maximum of two
+ *              such screens: not reproduced).
+ *   DRAW       mix64(seed ^ mix64((global_env << 40) ^ piece_counter) ^ 0x7E7215B10C5D20F7) % 7, then
+ *              piece_counter += 1. piece_counter is per env and is not reset by a new game (as Catch's
+ *              ball_counter), so a data-parallel shard draws what the union would draw.
+ *   reset      piece_counter = 0, next_piece = 1 + DRAW, then a new game.
+ *   new game   an empty board, the piece spawns from next_piece as above (so a game's first piece is the
+ *              previous game's next_piece), level = 1, lines = 0, speed = cfg.speed, speed_counter = 0. Then
+ *              (tetris_emulator.py:63-70, 97-105) w = mix64(seed ^ mix64((global_env << 40) ^ piece_counter)
+ *              ^ 0x57A27F0A17C0FFEE) % (max_start_wait + 1) times act(0) (piece_counter as it then stands, not
+ *              advanced by this draw), then four act(0) whose frames are the initial stacked state, oldest
+ *              first; rewards of these acts are dropped; then nexts = 0. (With max_start_wait <= 30 these
+ *              at most 34 acts cannot end the game: they lock at most two pieces on an empty board.)
+ *   macro-step, stacking: Catch's, with a clamped to [0, 4]: next(a) is run tab_rep[r] + 1 times (the
+ *              entry clamped to [0, 255]), the rewards summed, stopping at the first episode end, after which
+ *              a new game starts at once and the state returned is its initial state (all four stack
+ *              positions replaced). A macro-step plays at most tab_rep[r] + 1 + 34 acts.
+ *   render     84 x 84 from the reference's 288 x 396 screen (16 x 22 cells of 18 px) under a nearest
+ *              resize: output pixel (row i, column j) shows cell (cx, cy) = ((((2j+1) 12) / 7) / 18,
+ *              (((2i+1) 33) / 14) / 18). The colour id of a cell, later rules winning: 0; 8 where cx < 10
+ *              and cx % 2 == cy % 2 (the background grid); the board's cell where it is not 0; `piece` where
+ *              the falling piece has a non-zero cell; next_piece where the unrotated next piece, its
+ *              matrix's top-left at cell (11, 2), has one. No text; the separator line at source x = 181 is
+ *              hit by no sampled column. RGB of ids 0..8 (the reference's `colors`): (0,0,0), (255,85,85),
+ *              (100,200,115), (120,108,245), (255,140,50), (50,120,52), (146,202,73), (150,161,218),
+ *              (35,35,35). gray of ids 0..8: 0, 136, 160, 127, 164, 91, 171, 190, 35. Channel order is Catch's.
+ *
+ * A state from outside the rule is used with piece and next_piece clamped to [1, 7], rot to [0, 3], x to
+ * [0, 9], y to [0, 21], level to [1, 2^20], speed to >= 1, lines to [0, 2^28], speed_counter and nexts to
+ * [0, 2^30], and the board words masked to 30 bits. */
+typedef struct mt_tetris_config {
+  int32_t max_nexts;      /* default 2000 */
+  int32_t speed;          /* default 5 (the reference's) */
+  int32_t max_start_wait; /* default 0; 30 is the reference's random_start; at most 30 */
+} mt_tetris_config;
+/* Per-env state, 136 bytes, 8-byte aligned, in caller-owned memory; the field order is part of the ABI. */
+typedef struct mt_tetris_state {
+  uint32_t board[22];
+  int32_t piece, rot, x, y, next_piece, level, lines, speed, speed_counter, nexts;
+  uint64_t piece_counter;
+} mt_tetris_state;
+
+/* The entry points are Bricks' with this game's config and state: the same argument lists, layouts, NULL
+ * rules and clamping (a_idx to [0, 4]). MT_ERR_ARG before any launch for bad sizes (E < 1, env0 < 0, R < 1,
+ * T < 1, t outside [0, T)), depth not 1 or 3, max_nexts or speed < 1, max_start_wait outside [0, 30], out ==
+ * prev, out / prev / frames_out not 16-byte or state not 8-byte aligned, frames_out without push_count_out
+ * or the reverse, or a null required pointer. Capturable: no allocation, no synchronisation, no atomics. */
+int mt_tetris_reset(const mt_tetris_config *cfg, uint64_t seed, int env0, int E, int depth, mt_tetris_state *state,
+                    uint8_t *out_state0, mt_stream_t stream);
+int mt_tetris_step(const mt_tetris_config *cfg, uint64_t seed, int env0, int E, int depth, const int32_t *tab_rep,
+                   int R, const int32_t *a_idx, const int32_t *r_idx, mt_tetris_state *state, const uint8_t *prev,
+                   uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out, float *over_out,
+                   float *rm_out, int t, int T, mt_stream_t stream);
+/* The same rule for ONE env on HOST pointers; needs no GPU (NULL frame pointers: nothing is rendered). */
+int mt_tetris_reset_host(const mt_tetris_config *cfg, uint64_t seed, uint64_t global_env, int depth,
+                         mt_tetris_state *state, uint8_t *out_state0);
+int mt_tetris_step_host(const mt_tetris_config *cfg, uint64_t seed, uint64_t global_env, int depth,
+                        const int32_t *tab_rep, int R, int a, int r, mt_tetris_state *state, const uint8_t *prev,
+                        uint8_t *out, uint8_t *frames_out, int32_t *push_count_out, float *reward_out,
+                        float *over_out);
+
 /* ---- Device bookkeeping of one rollout (the learner's Bookkeeper.step, paac.py:154-205, as a kernel) ----
  * Everything a rollout of a device-resident game leaves for the host (global_step, the episode records,
  * the action / repetition histogram, the learning rate of its update) computed where the rollout ran, so

@@ -83,6 +83,20 @@ class mt_bricks_state(C.Structure):
                 ('serve_counter', C.c_uint64)]
 
 
+class mt_tetris_config(C.Structure):
+    """Tetris (include/manette_hip.h): the cap on an episode's nexts, the acts per gravity drop at level 1,
+    the most noop acts before a game's initial state."""
+    _fields_ = [('max_nexts', C.c_int32), ('speed', C.c_int32), ('max_start_wait', C.c_int32)]
+
+
+class mt_tetris_state(C.Structure):
+    """Per-env Tetris state, 136 bytes."""
+    _fields_ = [('board', C.c_uint32 * 22)] + \
+               [(n, C.c_int32) for n in ('piece', 'rot', 'x', 'y', 'next_piece', 'level', 'lines', 'speed',
+                                         'speed_counter', 'nexts')] + \
+               [('piece_counter', C.c_uint64)]
+
+
 class mt_book_words(C.Structure):
     """The device book's word block (include/manette_hip.h, "Device bookkeeping"), 40 bytes."""
     _fields_ = [(n, C.c_int64) for n in ('global_step', 'written', 'acked', 'nb_actions')] + \
@@ -207,6 +221,14 @@ _HIP_SIGS = {
                                   _P]),
     'mt_bricks_step_host': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
                                  C.POINTER(mt_bricks_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
+                                 C.POINTER(_F)]),
+    'mt_tetris_reset': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, _I, _I, _I, _P, _P, _P]),
+    'mt_tetris_step': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _I, _I, _P]),
+    'mt_tetris_reset_host': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, C.c_uint64, _I, C.POINTER(mt_tetris_state),
+                                  _P]),
+    'mt_tetris_step_host': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
+                                 C.POINTER(mt_tetris_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
                                  C.POINTER(_F)]),
     'mt_book_rollout': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
                              C.c_double, C.c_double, _P]),

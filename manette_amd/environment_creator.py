@@ -22,17 +22,20 @@ MINIMAL_ACTIONS = {
 
 # games with a device-resident environment (--runner device): the game lives in HBM, one kernel per macro-step
 DEVICE_GAMES = ('catch', 'bricks')
+# and the reference's own game with one (its rule is tetris.py's, not this project's)
+REFERENCE_DEVICE_GAMES = ('tetris',)
+ALL_DEVICE_GAMES = DEVICE_GAMES + REFERENCE_DEVICE_GAMES
 
 
 def has_device_env(game):
-    return str(game).lower() in DEVICE_GAMES
+    return str(game).lower() in ALL_DEVICE_GAMES
 
 
 class EnvironmentCreator(object):
     def __init__(self, args):
         game = args.game.lower()
-        if game == 'tetris' or game.endswith('-v0'):
-            raise NotImplementedError('gym / tetris emulators are out of scope (SURVEY.md §2)')
+        if game.endswith('-v0'):
+            raise NotImplementedError('gym emulators are out of scope (SURVEY.md §2)')
         self.game = game
         self.rgb = bool(getattr(args, 'rgb', False))
         self.rank_offset = int(getattr(args, 'env_id_offset', 0))
@@ -56,6 +59,17 @@ class EnvironmentCreator(object):
                                     serve_wait=int(getattr(args, 'bricks_serve_wait', bricks.DEFAULT_SERVE_WAIT)))
             self.create_environment = lambda i: bricks.BricksEmulator(self.rank_offset + i, **self.bricks_args)
             return
+        if game == 'tetris':
+            # the reference's own game (manette_amd/tetris.py), through the same two faces
+            from . import tetris
+            self.num_actions = tetris.NUM_ACTIONS
+            wait = tetris.RANDOM_START_WAIT if getattr(args, 'random_start', False) else tetris.DEFAULT_MAX_START_WAIT
+            self.tetris_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
+                                    max_nexts=int(getattr(args, 'tetris_max_nexts', tetris.DEFAULT_MAX_NEXTS)),
+                                    speed=int(getattr(args, 'tetris_speed', tetris.DEFAULT_SPEED)),
+                                    max_start_wait=wait)
+            self.create_environment = lambda i: tetris.TetrisEmulator(self.rank_offset + i, **self.tetris_args)
+            return
         self.num_actions = MINIMAL_ACTIONS.get(game, 18)
         self.create_environment = lambda i: SyntheticEmulator(self.rank_offset + i, self.num_actions,
                                                               rgb=self.rgb)
@@ -64,15 +78,18 @@ class EnvironmentCreator(object):
         """Envs [0, n_envs) of this rank (global ids offset by rank) as a device-resident environment."""
         if not has_device_env(self.game):
             raise ValueError('game %r has no device environment (--runner device serves: %s)'
-                             % (self.game, ', '.join(DEVICE_GAMES)))
+                             % (self.game, ', '.join(ALL_DEVICE_GAMES)))
         if self.game == 'bricks':
             from . import bricks
             return bricks.BricksDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.bricks_args)
+        if self.game == 'tetris':
+            from . import tetris
+            return tetris.TetrisDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.tetris_args)
         from . import catch
         return catch.CatchDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.catch_args)
 
     def create_bank(self, first_local, n_envs):
         """Native bank of envs [first_local, first_local+n) (global ids offset by rank)."""
-        if self.game in DEVICE_GAMES:
+        if self.game in ALL_DEVICE_GAMES:
             raise ValueError('game %r runs under --runner device or --runner python, not the native runner' % self.game)
         return SyntheticBank(self.rank_offset + first_local, n_envs, rgb=self.rgb)

@@ -11,8 +11,9 @@ Paths (args.runner):
             H2D from one pinned staging buffer and mt_preprocess builds the stacks (A2).
   'python'  reference-contract Python emulators (Runners / EmulatorRunner processes); finished
             84x84xC observations go H2D.
-  'device'  the game itself lives in HBM (-g catch, manette_amd/catch.py; -g bricks, manette_amd/bricks.py):
-            one kernel per macro-step steps, renders and stacks every env (mt_catch_step, mt_bricks_step);
+  'device'  the game itself lives in HBM (-g catch, manette_amd/catch.py; -g bricks, manette_amd/bricks.py;
+            -g tetris, manette_amd/tetris.py): one kernel per macro-step steps, renders and stacks every env
+            (mt_catch_step, mt_bricks_step, mt_tetris_step);
             with --sampling device a rollout is
             T x (forward -> draw -> env kernel) enqueued without a host synchronisation (_device_rollout);
             with --iteration_graph the rollout's bookkeeping is a kernel as well (mt_book_rollout, DeviceBook)
@@ -60,12 +61,12 @@ def check_arch_flags(args):
         raise ValueError('--bayes_native is for --arch BAYESIAN (got --arch %s)' % getattr(args, 'arch', None))
     # --runner device: the game lives in HBM (manette_amd/catch.py); games without a device env and the
     # LSTM frame store are refused; a device game has no native (host-thread) bank
-    from .environment_creator import DEVICE_GAMES, has_device_env
+    from .environment_creator import ALL_DEVICE_GAMES, has_device_env
     runner, game = getattr(args, 'runner', 'native'), getattr(args, 'game', 'pong')
     if runner == 'device':
         if not has_device_env(game):
             raise ValueError('--runner device needs a game with a device environment (-g %s), got -g %s'
-                             % (' | '.join(DEVICE_GAMES), game))
+                             % (' | '.join(ALL_DEVICE_GAMES), game))
         if getattr(args, 'arch', None) == 'LSTM':
             raise ValueError('--runner device does not serve --arch LSTM (its frame store is filled by the host path)')
         if getattr(args, 'bayes_native', False):

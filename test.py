@@ -9,16 +9,16 @@ Differences, each a fix or a missing dependency:
   * an emulator whose episode ended is not stepped again (ALE gives no reward after game over,
     the synthetic stand-in would keep streaming rewards);
   * Atari games run on the synthetic emulators (ALE absent, environment_creator.py); the device-resident
-    games are played on their host faces (-g catch: CatchEmulator, -g bricks: BricksEmulator, with the run's
-    --catch_* / --bricks_* config from args.json), so a checkpoint trained under --runner device is tested
-    on the same rule; gif output needs imageio (absent): -gn is accepted and reported as unavailable;
+    games are played on their host faces (-g catch: CatchEmulator, -g bricks: BricksEmulator, -g tetris:
+    TetrisEmulator, with the run's --catch_* / --bricks_* / --tetris_* config from args.json), so a checkpoint
+    trained under --runner device is tested on the same rule; gif output needs imageio (absent): -gn is accepted and reported as unavailable;
   * --runner device (this build; the default `host` is the loop above, untouched): the device-resident
     games are played where they live, -tc envs (global ids 0..tc-1, the host face's) times -ep episodes
     each, by manette_amd.evaluate.DeviceEvaluator: forward, draw, env kernel and the per-episode
     bookkeeping (mt_eval_step) enqueued with one host look per block of macro-steps. --greedy picks the
     argmax chooser (else the one args.json implies: multinomial or its e-greedy settings), --draw_seed
     fixes the draw stream (default: from the clock, as the host loop's). -np is not applied there: the
-    games randomise through their own ball / serve streams.
+    games randomise through their own ball / serve / piece streams.
 """
 import argparse
 import logging
@@ -57,7 +57,7 @@ def get_arg_parser():
     # this build
     parser.add_argument('--runner', default='host', choices=['host', 'device'],
                         help="host: the reference's loop on the emulators' host faces; device: a device-resident game "
-                             "(-g catch, -g bricks) evaluated in HBM (manette_amd/evaluate.py)", dest='test_runner')
+                             "(-g catch, -g bricks, -g tetris) evaluated in HBM (manette_amd/evaluate.py)", dest='test_runner')
     parser.add_argument('--greedy', action='store_true', help='--runner device: the argmax chooser (default: the one '
                         'the run\'s args.json implies)', dest='greedy')
     parser.add_argument('--draw_seed', default=None, type=int, help='--runner device: seed of the draw stream '
@@ -123,10 +123,10 @@ def run(args, max_macro_steps=None):
     args.random_seed = rng.randint(1000)
 
     if test_runner == 'device':
-        from manette_amd.environment_creator import DEVICE_GAMES, has_device_env
+        from manette_amd.environment_creator import ALL_DEVICE_GAMES, has_device_env
         if not has_device_env(args.game):
             raise ValueError('--runner device needs a game with a device environment (-g %s), got -g %s'
-                             % (' | '.join(DEVICE_GAMES), args.game))
+                             % (' | '.join(ALL_DEVICE_GAMES), args.game))
     explo_policy = ExplorationPolicy(args, test=False)
     network_creator, env_creator = train_cli.get_network_and_environment_creator(args, explo_policy)
     network = network_creator()

@@ -9,6 +9,11 @@ deterministic: counter-based draws, no float atomics. One JSON line per seed.
 
 --game bricks: the same for the device-resident Bricks (manette_amd/bricks.py) at its default config, the bar
 being 4 x the uniform-random policy's mean return (bricks_bar), and --max_seconds a wall-clock cap per seed.
+
+--game tetris: the device-resident Tetris (manette_amd/tetris.py) at its default config. Under clipped rewards
+the first thing to learn is that dropping pays, so the bar is on the reward per next(): the mean of return /
+length over the last 100 finished episodes, against the midpoint between the uniform-random policy's value and
+the always-drop policy's (tetris_bar).
 """
 import argparse
 import json
@@ -67,8 +72,34 @@ def bricks_bar(episodes=100, seed=0, **cfg):
     return 4.0 * bricks_random_policy_mean(episodes, seed, **cfg)
 
 
+def tetris_policy_rate(choose, episodes=100, seed=0, **cfg):
+    """Mean of return / length over `episodes` episodes of env 0 (mt_tetris_step_host) under choose() -> action."""
+    from manette_amd import _lib, tetris
+    c = tetris.config(**cfg)
+    st = _lib.mt_tetris_state()
+    tetris.host_reset(c, seed, 0, 1, st)
+    tab = np.zeros(1, np.int32)
+    rates, ret, n = [], 0.0, 0
+    while len(rates) < episodes:
+        rw, over, _ = tetris.host_step(c, seed, 0, 1, tab, choose(), 0, st)
+        ret += rw
+        n += 1
+        if over:
+            rates.append(ret / n)
+            ret, n = 0.0, 0
+    return float(np.mean(rates))
+
+
+def tetris_bar(episodes=100, seed=0, **cfg):
+    """The midpoint between the uniform-random policy's reward per next and the always-drop policy's."""
+    rs = np.random.RandomState(12345)
+    rand = tetris_policy_rate(lambda: int(rs.randint(5)), episodes, seed, **cfg)
+    drop = tetris_policy_rate(lambda: 3, episodes, seed, **cfg)
+    return 0.5 * (rand + drop)
+
+
 def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampling='device', max_rep=0, nb=1,
-                 iteration_graph=False, drain_every=None, game='catch'):
+                 iteration_graph=False, drain_every=None, game='catch', tetris_cfg=None):
     import train as cli
     from manette_amd.exploration_policy import ExplorationPolicy
     from manette_amd.paac import PAACLearner
@@ -77,6 +108,8 @@ def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampli
     a.runner, a.sampling, a.seed = 'device', sampling, seed
     a.max_repetition, a.nb_choices = max_rep, nb
     a.catch_lives, a.catch_max_balls = lives, max_balls
+    if tetris_cfg is not None:
+        a.tetris_max_nexts, a.tetris_speed = tetris_cfg
     a.iteration_graph, a.drain_every = iteration_graph, drain_every
     a.initial_lr, a.lr_annealing_steps = 0.02, 300000000  # pretrained/catcher/args.json
     a.debugging_folder = folder + '/'
@@ -89,9 +122,9 @@ def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampli
     return L
 
 
-def train_until(L, target, max_updates, every=0, window=100, max_seconds=None):
-    """Updates until the mean return of the last `window` finished episodes >= target (checked after
-    every update); returns (updates run, reached, curve [(update, mean)])."""
+def train_until(L, target, max_updates, every=0, window=100, max_seconds=None, per_next=False):
+    """Updates until the mean return (per_next: the mean of return / length) of the last `window` finished
+    episodes >= target (checked after every update); returns (updates run, reached, curve [(update, mean)])."""
     curve = []
     t0 = time.time()
     for u in range(1, max_updates + 1):
@@ -103,7 +136,10 @@ def train_until(L, target, max_updates, every=0, window=100, max_seconds=None):
         if L.iteration_graph:  # (the bar is checked after every update: one drain each)
             L.drain()
         tr = L.book.total_rewards
-        mean = float(np.mean(tr[-window:])) if len(tr) >= window else None
+        if per_next and len(tr) >= window:
+            mean = float(np.mean(np.asarray(tr[-window:], np.float64) / np.asarray(L.book.total_steps[-window:])))
+        else:
+            mean = float(np.mean(tr[-window:])) if len(tr) >= window else None
         if every and u % every == 0:
             curve.append((u, mean))
         if mean is not None and mean >= target:
@@ -120,29 +156,31 @@ def main():
     ap.add_argument('--ec', type=int, default=32)
     ap.add_argument('--lives', type=int, default=3)
     ap.add_argument('--max_balls', type=int, default=20)
-    ap.add_argument('--game', choices=['catch', 'bricks'], default='catch')
+    ap.add_argument('--game', choices=['catch', 'bricks', 'tetris'], default='catch')
     ap.add_argument('--max_seconds', type=float, default=None, help='stop a seed after this many seconds')
     ap.add_argument('--iteration_graph', action='store_true', help='train under --iteration_graph (drained after '
                     'every update, the bar being checked there): the arithmetic is the eager path\'s')
     args = ap.parse_args()
     import torch
     bricks_game = args.game == 'bricks'
-    target = bricks_bar() if bricks_game else bar(args.lives, args.max_balls)
+    tetris_game = args.game == 'tetris'
+    target = bricks_bar() if bricks_game else tetris_bar() if tetris_game else bar(args.lives, args.max_balls)
     for seed in args.seeds:
         with tempfile.TemporaryDirectory() as tmp:
             L = make_learner(tmp, seed, ec=args.ec, lives=args.lives, max_balls=args.max_balls, game=args.game,
                              iteration_graph=args.iteration_graph, drain_every=1 if args.iteration_graph else None)
             t0 = time.time()
-            n, reached, curve = train_until(L, target, args.max_updates, args.every, max_seconds=args.max_seconds)
+            n, reached, curve = train_until(L, target, args.max_updates, args.every, max_seconds=args.max_seconds,
+                                            per_next=tetris_game)
             torch.cuda.synchronize()
             dt = time.time() - t0
             L.cleanup()
         extra = {'iteration_graph': True} if args.iteration_graph else {}
-        if bricks_game:
-            extra['game'] = 'bricks'
+        if bricks_game or tetris_game:
+            extra['game'] = args.game
         print(json.dumps(dict(seed=seed, bar=target, reached=reached, updates=n, seconds=round(dt, 2), **extra,
                               env_steps=n * args.ec * 5, episodes=len(L.book.total_rewards),
-                              curve=[(u, None if m is None else round(m, 2)) for u, m in curve])), flush=True)
+                              curve=[(u, None if m is None else round(m, 3 if tetris_game else 2)) for u, m in curve])), flush=True)
 
 
 if __name__ == '__main__':

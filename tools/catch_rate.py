@@ -17,6 +17,7 @@
   python tools/catch_rate.py [--updates 300] [--skip_kernel] [--skip_rollout] [--skip_graph] [--game bricks]
 One JSON line per measurement. --game bricks measures the device-resident Bricks (manette_amd/bricks.py) the
 same way: its kernel lines carry bricks_step_us beside catch_step_us and preprocess_resized_us of the same run.
+--game tetris (manette_amd/tetris.py) adds tetris_step_us to those lines.
 """
 import argparse
 import json
@@ -39,7 +40,7 @@ def _tag(game):
 def kernel_times(inner=50, reps=5, game='catch'):
     import torch
     import bench
-    from manette_amd import bricks, catch, network as devnet
+    from manette_amd import bricks, catch, network as devnet, tetris
     for E in (32, 64):
         for depth in (1, 3):
             for R in (1, 11):
@@ -68,7 +69,7 @@ def kernel_times(inner=50, reps=5, game='catch'):
 
                 t_env = bench.graph_time(step, inner, reps)
                 t_stack = bench.graph_time(stack, inner, reps)
-                if game == 'bricks':  # the same buffers, indices and table under the other game (a in 0..3)
+                if game in ('bricks', 'tetris'):  # the same buffers, indices and table under the other game (a in 0..3)
                     bdev = bricks.BricksDevice(E, tab, seed=1, rgb=depth == 3)
                     ab = torch.from_numpy(rs.randint(0, 4, E).astype(np.int32)).cuda()
                     bdev.reset(bufs[0])
@@ -80,7 +81,22 @@ def kernel_times(inner=50, reps=5, game='catch'):
                         k[0] += 1
 
                     t_b = bench.graph_time(bstep, inner, reps)
-                    print(json.dumps(dict(what='kernel', game='bricks', E=E, depth=depth, R=R,
+                    extra = {}
+                    if game == 'tetris':  # and under the third game (a in 0..4), some way into its episodes
+                        tdev = tetris.TetrisDevice(E, tab, seed=1, rgb=depth == 3)
+                        at = torch.from_numpy(rs.randint(0, 5, E).astype(np.int32)).cuda()
+                        tdev.reset(bufs[0])
+                        for _ in range(40):
+                            tdev.step(at, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)
+
+                        def tstep():
+                            tdev.step(at, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
+                            k[0] += 1
+
+                        t_t = bench.graph_time(tstep, inner, reps)
+                        extra = dict(tetris_step_us=round(float(np.median(t_t)), 2),
+                                     tetris_step_all=[round(x, 2) for x in t_t])
+                    print(json.dumps(dict(what='kernel', game=game, E=E, depth=depth, R=R, **extra,
                                           bricks_step_us=round(float(np.median(t_b)), 2),
                                           catch_step_us=round(float(np.median(t_env)), 2),
                                           preprocess_resized_us=round(float(np.median(t_stack)), 2),
@@ -186,7 +202,7 @@ def main():
     ap.add_argument('--skip_rollout', action='store_true')
     ap.add_argument('--skip_graph', action='store_true')
     ap.add_argument('--drain_every', type=int, default=None)
-    ap.add_argument('--game', choices=['catch', 'bricks'], default='catch')
+    ap.add_argument('--game', choices=['catch', 'bricks', 'tetris'], default='catch')
     args = ap.parse_args()
     if not args.skip_kernel:
         kernel_times(game=args.game)

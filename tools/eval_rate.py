@@ -156,7 +156,7 @@ def wall_times(game, arch, n, figar, rgb, rounds=3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--game', choices=['catch', 'bricks'], default='catch')
+    ap.add_argument('--game', choices=['catch', 'bricks', 'tetris'], default='catch')
     ap.add_argument('--arch', default='NIPS')
     ap.add_argument('--n', type=int, default=64)
     ap.add_argument('--figar', action='store_true')

@@ -5,6 +5,8 @@ Extra flags (this build only): --runner {native,python,device}, --sampling {host
 --staging {resized,in_place,zero_copy,copy,pooled}, --no_pipeline, --seed, --bayes_native,
 --catch_lives, --catch_max_balls (-g catch: the device-resident game, manette_amd/catch.py),
 --bricks_lives, --bricks_max_nexts, --bricks_serve_wait (-g bricks: the second one, manette_amd/bricks.py),
+--tetris_max_nexts, --tetris_speed (-g tetris: the reference's own game, manette_amd/tetris.py; --random_start gives
+its new games up to 30 noop acts before their initial state),
 --iteration_graph, --drain_every (the device game's whole iteration as one replayed graph),
 --eval_every, --eval_envs, --eval_episodes, --eval_greedy (device-resident evaluation during training).
 Multi-GPU: launch one process per GPU with torch.distributed.run; each rank trains
@@ -44,10 +46,10 @@ def validate_args(args):
     if envs < 1 or episodes < 1:
         raise ValueError('--eval_envs and --eval_episodes must be >= 1, got %d and %d' % (envs, episodes))
     if every > 0 or getattr(args, 'eval_greedy', False):
-        from manette_amd.environment_creator import DEVICE_GAMES, has_device_env
+        from manette_amd.environment_creator import ALL_DEVICE_GAMES, has_device_env
         if not has_device_env(getattr(args, 'game', 'pong')):
             raise ValueError('--eval_every / --eval_greedy evaluate in device memory and need a game with a device '
-                             'environment (-g %s), got -g %s' % (' | '.join(DEVICE_GAMES), args.game))
+                             'environment (-g %s), got -g %s' % (' | '.join(ALL_DEVICE_GAMES), args.game))
 
 
 def main(args):
@@ -166,7 +168,7 @@ def get_arg_parser():
     parser.add_argument('-ec', '--emulator_counts', default=32, type=int, help="The amount of emulators per agent. Default is 32.", dest="emulator_counts")
     parser.add_argument('-ew', '--emulator_workers', default=8, type=int, help="The amount of emulator workers per agent. Default is 8.", dest="emulator_workers")
     parser.add_argument('-df', '--debugging_folder', default='logs/', type=str, help="Folder where to save the debugging information.", dest="debugging_folder")
-    parser.add_argument('-rs', '--random_start', action='store_true', help="Whether or not to start with 30 noops for each env. Default True", dest="random_start")
+    parser.add_argument('-rs', '--random_start', action='store_true', help="Whether or not to start with 30 noops for each env. Default True (-g tetris: each new game first plays up to 30 noop acts, drawn per game)", dest="random_start")
     parser.add_argument('--egreedy', action='store_true', help="If True, e-greedy policy is used to  choose actions", dest="egreedy")
     parser.add_argument('--epsilon', default=0.05, type=float, help="Epsilon for the egreedy policy", dest='epsilon')
     parser.add_argument('--softmax_temp', default=1.0, type=float, help="Softmax temperature for the Boltzmann action policy", dest='softmax_temp')
@@ -180,7 +182,9 @@ def get_arg_parser():
     parser.add_argument('--activation', default='relu', type=str, help="activation function for the network", dest="activation")
     parser.add_argument('--alpha_leaky_relu', default=0.1, type=float, help="coef for leaky relu", dest="alpha_leaky_relu")
     # this build
-    parser.add_argument('--runner', default='native', choices=['native', 'python', 'device'], help='native: C++ emulator threads + GPU preprocess; python: reference-contract emulator processes; device: the game lives in HBM, one kernel per macro-step steps, renders and stacks it (-g catch or -g bricks; not --arch LSTM)', dest='runner')
+    parser.add_argument('--runner', default='native', choices=['native', 'python', 'device'], help='native: C++ emulator threads + GPU preprocess; python: reference-contract emulator processes; device: the game lives in HBM, one kernel per macro-step steps, renders and stacks it (-g catch, -g bricks or -g tetris; not --arch LSTM)', dest='runner')
+    parser.add_argument('--tetris_max_nexts', default=2000, type=int, help='-g tetris: the cap on an episode\'s emulator steps (next() calls)', dest='tetris_max_nexts')
+    parser.add_argument('--tetris_speed', default=5, type=int, help='-g tetris: acts per gravity drop at level 1 (the reference\'s 5)', dest='tetris_speed')
     parser.add_argument('--catch_lives', default=3, type=int, help='-g catch: misses that end an episode', dest='catch_lives')
     parser.add_argument('--catch_max_balls', default=20, type=int, help='-g catch: balls of an episode', dest='catch_max_balls')
     parser.add_argument('--bricks_lives', default=3, type=int, help='-g bricks: lost balls that end an episode', dest='bricks_lives')
@@ -209,7 +213,7 @@ def get_arg_parser():
     parser.add_argument('--drain_every', default=None, type=int, help='--iteration_graph: iterations launched back to '
                         'back between two drains of the device book (default max(1, 2048 // ec), the logging interval)',
                         dest='drain_every')
-    parser.add_argument('--eval_every', default=0, type=int, help='-g catch / -g bricks: every this many global steps '
+    parser.add_argument('--eval_every', default=0, type=int, help='-g catch / -g bricks / -g tetris: every this many global steps '
                         '(0 = off) the chief plays --eval_envs x --eval_episodes fixed games in device memory with the '
                         'current parameters (manette_amd/evaluate.py) and writes eval/* scalars; also once at the end. '
                         'With --iteration_graph: at the first drain at or past the multiple', dest='eval_every')
