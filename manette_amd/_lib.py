@@ -206,30 +206,6 @@ _HIP_SIGS = {
     'mt_graph_end': (_I, [_P, C.POINTER(_P)]),
     'mt_graph_launch': (_I, [_P, _P]),
     'mt_graph_destroy': (_I, [_P]),
-    'mt_catch_reset': (_I, [C.POINTER(mt_catch_config), C.c_uint64, _I, _I, _I, _P, _P, _P]),
-    'mt_catch_step': (_I, [C.POINTER(mt_catch_config), C.c_uint64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                           _P, _P, _I, _I, _P]),
-    'mt_catch_reset_host': (_I, [C.POINTER(mt_catch_config), C.c_uint64, C.c_uint64, _I, C.POINTER(mt_catch_state),
-                                 _P]),
-    'mt_catch_step_host': (_I, [C.POINTER(mt_catch_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
-                                C.POINTER(mt_catch_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
-                                C.POINTER(_F)]),
-    'mt_bricks_reset': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, _I, _I, _I, _P, _P, _P]),
-    'mt_bricks_step': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                            _P, _P, _I, _I, _P]),
-    'mt_bricks_reset_host': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, C.c_uint64, _I, C.POINTER(mt_bricks_state),
-                                  _P]),
-    'mt_bricks_step_host': (_I, [C.POINTER(mt_bricks_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
-                                 C.POINTER(mt_bricks_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
-                                 C.POINTER(_F)]),
-    'mt_tetris_reset': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, _I, _I, _I, _P, _P, _P]),
-    'mt_tetris_step': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                            _P, _P, _I, _I, _P]),
-    'mt_tetris_reset_host': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, C.c_uint64, _I, C.POINTER(mt_tetris_state),
-                                  _P]),
-    'mt_tetris_step_host': (_I, [C.POINTER(mt_tetris_config), C.c_uint64, C.c_uint64, _I, _P, _I, _I, _I,
-                                 C.POINTER(mt_tetris_state), _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(_F),
-                                 C.POINTER(_F)]),
     'mt_book_rollout': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
                              C.c_double, C.c_double, _P]),
     'mt_book_rollout_host': (_I, [C.POINTER(mt_book_state), _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64,
@@ -241,6 +217,20 @@ _HIP_SIGS = {
     'mt_eval_step_host': (_I, [C.POINTER(mt_eval_state), _P, _P, _P, _P, _I]),
     'mt_eval_summarize_host': (_I, [C.POINTER(mt_eval_state), _P]),
 }
+
+# The device games (include/manette_hip.h: "Catch", "Bricks", "Tetris") share one contract: four entry points
+# each, whose signatures differ in the game's config and state structs only.
+GAME_ENTRY_POINTS = ('reset', 'step', 'reset_host', 'step_host')
+for _game, _cfg, _state in (('catch', mt_catch_config, mt_catch_state), ('bricks', mt_bricks_config, mt_bricks_state),
+                            ('tetris', mt_tetris_config, mt_tetris_state)):
+    _head = [C.POINTER(_cfg), C.c_uint64]
+    _HIP_SIGS.update({
+        'mt_%s_reset' % _game: (_I, _head + [_I, _I, _I, _P, _P, _P]),
+        'mt_%s_step' % _game: (_I, _head + [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+        'mt_%s_reset_host' % _game: (_I, _head + [C.c_uint64, _I, C.POINTER(_state), _P]),
+        'mt_%s_step_host' % _game: (_I, _head + [C.c_uint64, _I, _P, _I, _I, _I, C.POINTER(_state), _P, _P, _P,
+                                                 C.POINTER(C.c_int32), C.POINTER(_F), C.POINTER(_F)]),
+    })
 
 _HOST_SIGS = {
     'mh_last_error': (C.c_char_p, []),

@@ -12,9 +12,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-HIP_SOURCES = ['net.hip', 'misc.hip', 'rollout.hip', 'comm.hip', 'env.hip', 'book.hip', 'bricks.hip', 'eval.hip', 'tetris.hip']
+HIP_SOURCES = ['net.hip', 'misc.hip', 'rollout.hip', 'comm.hip', 'catch.hip', 'book.hip', 'bricks.hip', 'eval.hip', 'tetris.hip']
 HIP_HEADERS = ['common.h', 'gemm.h', 'jobs.h', 'nips_bwd.h', 'trunk_fused.h', 'arch.h', 'heads.h', 'lstm.h', 'dconv.h',
-               'nature_bwd.h', 'bayes.h', 'bricks.h', 'tetris.h']
+               'nature_bwd.h', 'bayes.h', 'catch.h', 'bricks.h', 'tetris.h', 'device_game.h']
 HOST_SOURCES = ['runner.cpp', 'crc32c.cpp']
 HIP_LIB = os.path.join(HERE, 'libmanette_hip.so')
 PROBE_LIB = os.path.join(HERE, 'libmanette_hip_probe.so')

@@ -1,28 +1,13 @@
 """Catch: a small real game (a paddle, falling balls, lives, three actions) whose rule is written out
-in include/manette_hip.h ("Catch"). Two faces of the same rule:
-
-  * CatchEmulator: the reference contract (BaseEnvironment) on the host restatement
-    (mt_catch_reset_host / mt_catch_step_host, no GPU needed) — the Python runner, test.py, CPU paths;
-  * CatchDevice: every env of a learner in HBM, stepped, rendered and stacked by one kernel per
-    macro-step (mt_catch_reset / mt_catch_step) — the device runner of PAACLearner.
-
-Both key an env's ball stream on (seed, global env id), so they play the same games.
+in include/manette_hip.h ("Catch"). Its description, and its two faces (manette_amd/device_game.py) under
+the game's own names: CatchEmulator on the host restatement, CatchDevice in HBM. Both key an env's ball
+stream on (seed, global env id), so they play the same games.
 """
-import ctypes as C
-
-import numpy as np
-
-from . import _lib
-from .environment import BaseEnvironment
+from . import device_game
 
 NUM_ACTIONS = 3
 DEFAULT_LIVES = 3
 DEFAULT_MAX_BALLS = 20
-STATE_BYTES = C.sizeof(_lib.mt_catch_state)
-
-
-def config(lives=DEFAULT_LIVES, max_balls=DEFAULT_MAX_BALLS):
-    return _lib.mt_catch_config(int(lives), int(max_balls))
 
 
 def max_episode_nexts(cfg):
@@ -33,95 +18,9 @@ def max_episode_nexts(cfg):
     return (38 * int(cfg.max_balls) + 3) // 4
 
 
-def host_reset(cfg, seed, global_env, depth, state, out=None):
-    """A new game (ball_counter = 0) into `state`; out (84, 84, 4*depth) uint8 or None."""
-    _lib.check(_lib.hip().mt_catch_reset_host(C.byref(cfg), C.c_uint64(seed), C.c_uint64(global_env), depth,
-                                              C.byref(state), None if out is None else out.ctypes.data_as(C.c_void_p)),
-               'mt_catch_reset_host')
-
-
-def host_step(cfg, seed, global_env, depth, tab_rep, a, r, state, prev=None, out=None, frames=None):
-    """One macro-step on the host. tab_rep: contiguous int32 array. Returns (reward, over, pushes)."""
-    p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
-    rw, ov, cnt = C.c_float(), C.c_float(), C.c_int32()
-    _lib.check(_lib.hip().mt_catch_step_host(C.byref(cfg), C.c_uint64(seed), C.c_uint64(global_env), depth,
-                                             p(tab_rep), len(tab_rep), int(a), int(r), C.byref(state), p(prev), p(out),
-                                             p(frames), C.byref(cnt), C.byref(rw), C.byref(ov)), 'mt_catch_step_host')
-    return rw.value, ov.value != 0.0, cnt.value
-
-
-class CatchEmulator(BaseEnvironment):
-    """The reference's emulator contract: next(action) -> (stacked observation, reward, is_terminal).
-    An episode end starts the next game at once (the rule's macro-step), so the observation returned
-    with is_terminal is already the new game's initial state, which get_initial_state() then hands
-    out again without playing anything (emulator_runner.py:24-41 calls it right after)."""
-
-    _ONE = np.zeros(1, dtype=np.int32)  # the repetition table of a single next()
-
-    def __init__(self, global_env_id, seed=0, rgb=False, lives=DEFAULT_LIVES, max_balls=DEFAULT_MAX_BALLS):
-        self.depth = 3 if rgb else 1
-        self.global_env = int(global_env_id)
-        self.seed = int(seed)
-        self.cfg = config(lives, max_balls)
-        self.state = _lib.mt_catch_state()
-        self.obs = np.zeros((84, 84, 4 * self.depth), dtype=np.uint8)
-        self._fresh = False  # obs is an initial state nobody asked for yet
-
-    def get_initial_state(self):
-        if not self._fresh:  # the first game (or a restart asked for mid-episode): from ball_counter 0
-            host_reset(self.cfg, self.seed, self.global_env, self.depth, self.state, self.obs)
-        self._fresh = False
-        return self.obs.copy()
-
-    def next(self, action):
-        out = np.empty_like(self.obs)
-        reward, over, _ = host_step(self.cfg, self.seed, self.global_env, self.depth, self._ONE, action, 0,
-                                    self.state, self.obs, out)
-        self.obs = out
-        self._fresh = over
-        return out.copy(), reward, over
-
-    def get_legal_actions(self):
-        return np.arange(NUM_ACTIONS)
-
-    def get_noop(self):
-        return 0
-
-
-class CatchDevice(object):
-    """Envs [env0, env0 + E) in device memory: owns the state buffer and the repetition table."""
-
-    def __init__(self, E, tab_rep, seed=0, env0=0, rgb=False, lives=DEFAULT_LIVES, max_balls=DEFAULT_MAX_BALLS,
-                 device='cuda'):
-        import torch
-        self.E, self.env0, self.seed = int(E), int(env0), int(seed)
-        self.depth = 3 if rgb else 1
-        self.cfg = config(lives, max_balls)
-        self.tab_rep = torch.tensor(list(tab_rep), dtype=torch.int32, device=device)
-        self.R = int(self.tab_rep.numel())
-        self.state = torch.zeros(self.E, STATE_BYTES, dtype=torch.uint8, device=device)
-
-    def reset(self, out):
-        """A new game for every env; out [E][84][84][4*depth] receives the stacked initial states."""
-        from .network import _ptr, _stream
-        assert out.is_contiguous() and out.numel() == self.E * 84 * 84 * 4 * self.depth
-        _lib.check(_lib.hip().mt_catch_reset(C.byref(self.cfg), C.c_uint64(self.seed), self.env0, self.E, self.depth,
-                                             _ptr(self.state), _ptr(out), _stream()), 'mt_catch_reset')
-
-    def step(self, a_idx, r_idx, prev, out, reward, over, rm, t, T, frames=None, push_count=None):
-        """One macro-step of every env (enqueued on the current stream; no sync): a_idx, r_idx [E] int32,
-        prev -> out stacked states, reward / over [E] fp32, rm [2][T][E] fp32 (row t written)."""
-        from .network import _ptr, _stream
-        assert prev.is_contiguous() and out.is_contiguous() and rm.is_contiguous()
-        _lib.check(_lib.hip().mt_catch_step(C.byref(self.cfg), C.c_uint64(self.seed), self.env0, self.E, self.depth,
-                                            _ptr(self.tab_rep), self.R, _ptr(a_idx), _ptr(r_idx), _ptr(self.state),
-                                            _ptr(prev), _ptr(out), _ptr(frames), _ptr(push_count), _ptr(reward),
-                                            _ptr(over), _ptr(rm), int(t), int(T), _stream()), 'mt_catch_step')
-
-    def state_array(self):
-        """The envs' states as a host array of mt_catch_state records (synchronises)."""
-        return np.frombuffer(self.state.cpu().numpy().tobytes(), dtype=STATE_DTYPE)
-
-
-STATE_DTYPE = np.dtype([(n, np.int32) for n in ('paddle_x', 'ball_x', 'ball_y', 'ball_dx', 'misses', 'balls')] +
-                       [('ball_counter', np.uint64)])
+GAME = device_game.Game('catch', NUM_ACTIONS, [('lives', DEFAULT_LIVES), ('max_balls', DEFAULT_MAX_BALLS)],
+                        max_episode_nexts)
+STATE_BYTES, STATE_DTYPE = GAME.state_bytes, GAME.state_dtype
+assert STATE_DTYPE.itemsize == STATE_BYTES == 32
+config, host_reset, host_step = GAME.config, GAME.host_reset, GAME.host_step
+CatchEmulator, CatchDevice = GAME.Emulator, GAME.Device

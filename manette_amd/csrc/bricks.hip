@@ -2,34 +2,11 @@
 // catch_kernel's shape: one kernel per macro-step runs the game logic of every env, renders its pushed
 // frames and writes the next stacked state straight into the rollout's state ring.
 #include "bricks.h"
+#include "device_game.h"
 
 namespace mt {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint32_t sgpr_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t sgpr_u64(uint64_t v) {
-  return (uint64_t)sgpr_u((uint32_t)v) | ((uint64_t)sgpr_u((uint32_t)(v >> 32)) << 32);
-}
-
-// The rows of the field (an 84-bit mask in two words) that any sprite of a pushed snapshot touches.
-struct Rows84 {
-  uint64_t lo, hi;
-};
-// bits (<= 4 wide) are set from `start` <= 81
-__device__ __forceinline__ void rows_or(Rows84 &m, int start, uint64_t bits) {
-  if (start < 64) {
-    m.lo |= bits << start;
-    if (start > 0) m.hi |= bits >> (64 - start);
-  } else {
-    m.hi |= bits << (start - 64);
-  }
-}
-__device__ __forceinline__ bool rows_bit(const Rows84 &m, int i) {
-  return ((i < 64 ? m.lo >> (i & 63) : m.hi >> ((i - 64) & 63)) & 1ull) != 0;
-}
 __device__ __forceinline__ void rows_of_snap(Rows84 &m, const BricksSnap &sn) {
   rows_or(m, (int)((sn.pos >> 16) & 0xffu), 3);  // the ball's 2 rows from ball_y <= 79
 #pragma unroll
@@ -41,30 +18,12 @@ __device__ __forceinline__ void rows_of_push(Rows84 &m, const BricksPush &p) {
   rows_of_snap(m, p.b);
 }
 
-// The bytes of 16-byte piece q of push p's own frame [84][84][DEPTH].
-template <int DEPTH>
-__device__ __forceinline__ u32x4 frame_piece(int q, const BricksPush &p) {
-  uint32_t w[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    w[k] = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int byte = 16 * q + 4 * k + b, pix = byte / DEPTH, ch = byte - pix * DEPTH;
-      const int y = pix / 84, x = pix - y * 84;
-      w[k] |= bricks_value<DEPTH>(x, y, ch, bricks_pixel<DEPTH>(x, y, ch), p) << (8 * b);
-    }
-  }
-  u32x4 v;
-  v.x = w[0];
-  v.y = w[1];
-  v.z = w[2];
-  v.w = w[3];
-  return v;
-}
 template <int DEPTH>
 __device__ __forceinline__ void write_frame(u32x4 *dst, const BricksPush &p) {
-  for (int q = threadIdx.x; q < 84 * 84 * DEPTH / 16; q += 256) dst[q] = frame_piece<DEPTH>(q, p);
+  for (int q = threadIdx.x; q < 84 * 84 * DEPTH / 16; q += 256)
+    dst[q] = frame_piece<DEPTH>(q, [&](int x, int y, int ch) {
+      return bricks_value<DEPTH>(x, y, ch, bricks_pixel<DEPTH>(x, y, ch), p);
+    });
 }
 
 // One workgroup per env. Every wave runs the env's game logic itself: it depends on blockIdx only, so
@@ -109,22 +68,15 @@ __global__ __launch_bounds__(256) void bricks_kernel(mt_bricks_config cfg, uint6
     s.reserved = 0;
     s.serve_counter = sgpr_u64(ld.serve_counter);
     int a = sgpr(a_idx[e]), r = sgpr(r_idx[e]);
-    a = a < 0 ? 0 : (a > 3 ? 3 : a);
-    r = r < 0 ? 0 : (r > R - 1 ? R - 1 : r);
-    int rep = sgpr(tab_rep[r]);
-    rep = rep < 0 ? 0 : (rep > 255 ? 255 : rep);
+    a = clamp_index(a, 4);  // (Bricks::kActions)
+    r = clamp_index(r, R);
+    const int rep = clamp_index(sgpr(tab_rep[r]), 256);
     bricks_macro_step(cfg, seed, genv, s, a, rep + 1, tr, &reward, &over);
   }
   if (threadIdx.x == 0) {
     state[e] = s;
-    if constexpr (!RESET) {
-      const float rw = (float)reward;
-      reward_out[e] = rw;
-      over_out[e] = over ? 1.f : 0.f;
-      rm_out[(size_t)t * E + e] = rw > 1.f ? 1.f : (rw < -1.f ? -1.f : rw);
-      rm_out[((size_t)T + t) * E + e] = over ? 0.f : 1.f;
-      if (push_count_out) push_count_out[e] = tr.count;
-    }
+    if constexpr (!RESET)
+      write_step_outputs(e, E, reward, over, tr.count, push_count_out, reward_out, over_out, rm_out, t, T);
   }
   constexpr int N16 = 84 * 84 * DEPTH / 4;  // 16-byte pieces of one env's state (4 words each)
   const size_t base = (size_t)e * N16;
@@ -169,37 +121,40 @@ __global__ __launch_bounds__(256) void bricks_kernel(mt_bricks_config cfg, uint6
   }
 }
 
-int bricks_check(const mt_bricks_config *cfg, int depth, const char *who) {
-  MT_CHECK_ARG(cfg != nullptr, "%s: null config", who);
-  MT_CHECK_ARG(depth == 1 || depth == 3, "%s: depth must be 1 or 3", who);
-  MT_CHECK_ARG(cfg->lives >= 1 && cfg->max_nexts >= 1 && cfg->serve_wait >= 0,
-               "%s: lives and max_nexts must be >= 1 and serve_wait >= 0", who);
-  return MT_OK;
-}
-
-// Host render of one env's stacked state / frames from a trace (the kernel's word and byte functions).
-template <int DEPTH>
-void host_stack(const BricksTrace &tr, const uint8_t *prev, uint8_t *out) {
-  for (int w = 0; w < 84 * 84 * DEPTH; ++w) {
-    uint32_t pw = 0;
-    if (tr.count < 4) memcpy(&pw, prev + 4 * (size_t)w, 4);
-    const uint32_t v = bricks_word<DEPTH>(w, pw, tr);
-    memcpy(out + 4 * (size_t)w, &v, 4);
+// What device_game.h needs of Bricks.
+struct Bricks {
+  static constexpr const char *name = "bricks";
+  typedef mt_bricks_config Config;
+  typedef mt_bricks_state State;
+  typedef BricksTrace Trace;
+  static constexpr int kActions = 4;
+  static constexpr const char *config_rule = "lives and max_nexts must be >= 1 and serve_wait >= 0";
+  static bool config_ok(const Config &cfg) { return cfg.lives >= 1 && cfg.max_nexts >= 1 && cfg.serve_wait >= 0; }
+  // (a new game draws nothing: the first serve hashes seed and genv)
+  static void new_game(const Config &cfg, uint64_t, uint64_t, State &s, Trace &tr) { bricks_new_game(cfg, s, tr); }
+  static void macro_step(const Config &cfg, uint64_t seed, uint64_t genv, State &s, int a, int n, Trace &tr,
+                         int *reward, bool *over) {
+    s.bricks_hi &= kBricksFullHi;
+    s.reserved = 0;
+    bricks_macro_step(cfg, seed, genv, s, a, n, tr, reward, over);
   }
-}
-template <int DEPTH>
-void host_frames(const BricksTrace &tr, uint8_t *frames) {
-  const BricksPush *q[4] = {&tr.q0, &tr.q1, &tr.q2, &tr.q3};
-  for (int j = 0; j < tr.count; ++j) {
-    const BricksPush &p = *q[4 - tr.count + j];
-    uint8_t *f = frames + (size_t)j * 84 * 84 * DEPTH;
-    for (int pix = 0; pix < 84 * 84; ++pix)
-      for (int ch = 0; ch < DEPTH; ++ch) {
-        const int x = pix % 84, y = pix / 84;
-        f[pix * DEPTH + ch] = (uint8_t)bricks_value<DEPTH>(x, y, ch, bricks_pixel<DEPTH>(x, y, ch), p);
-      }
+  template <int DEPTH>
+  static uint32_t word(int w, uint32_t prev_word, const Trace &tr) {
+    return bricks_word<DEPTH>(w, prev_word, tr);
   }
-}
+  static const BricksPush *push(const Trace &tr, int j) {
+    const BricksPush *q[4] = {&tr.q0, &tr.q1, &tr.q2, &tr.q3};
+    return q[4 - tr.count + j];
+  }
+  template <int DEPTH>
+  static uint32_t value(int x, int y, int ch, const BricksPush *p) {
+    return bricks_value<DEPTH>(x, y, ch, bricks_pixel<DEPTH>(x, y, ch), *p);
+  }
+  static GameKernel<Bricks> kernel(int depth, bool reset) {
+    return reset ? (depth == 1 ? bricks_kernel<1, true> : bricks_kernel<3, true>)
+                 : (depth == 1 ? bricks_kernel<1, false> : bricks_kernel<3, false>);
+  }
+};
 
 }  // namespace
 }  // namespace mt
@@ -208,18 +163,7 @@ using namespace mt;
 
 extern "C" int mt_bricks_reset(const mt_bricks_config *cfg, uint64_t seed, int env0, int E, int depth,
                                mt_bricks_state *state, uint8_t *out_state0, mt_stream_t stream) {
-  if (int rc = bricks_check(cfg, depth, "mt_bricks_reset")) return rc;
-  MT_CHECK_ARG(E >= 1 && env0 >= 0, "mt_bricks_reset: E must be >= 1 and env0 >= 0");
-  MT_CHECK_ARG(state && out_state0, "mt_bricks_reset: null argument");
-  MT_CHECK_ARG(((uintptr_t)out_state0 & 15) == 0 && ((uintptr_t)state & 7) == 0, "mt_bricks_reset: misaligned buffer");
-  if (depth == 1)
-    hipLaunchKernelGGL((bricks_kernel<1, true>), dim3(E), dim3(256), 0, (hipStream_t)stream, *cfg, seed, env0, nullptr, 1,
-                       nullptr, nullptr, state, nullptr, out_state0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1);
-  else
-    hipLaunchKernelGGL((bricks_kernel<3, true>), dim3(E), dim3(256), 0, (hipStream_t)stream, *cfg, seed, env0, nullptr, 1,
-                       nullptr, nullptr, state, nullptr, out_state0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1);
-  MT_LAUNCHED();
-  return MT_OK;
+  return game_reset<Bricks>(cfg, seed, env0, E, depth, state, out_state0, stream);
 }
 
 extern "C" int mt_bricks_step(const mt_bricks_config *cfg, uint64_t seed, int env0, int E, int depth,
@@ -227,78 +171,19 @@ extern "C" int mt_bricks_step(const mt_bricks_config *cfg, uint64_t seed, int en
                               mt_bricks_state *state, const uint8_t *prev, uint8_t *out, uint8_t *frames_out,
                               int32_t *push_count_out, float *reward_out, float *over_out, float *rm_out, int t, int T,
                               mt_stream_t stream) {
-  if (int rc = bricks_check(cfg, depth, "mt_bricks_step")) return rc;
-  MT_CHECK_ARG(E >= 1 && env0 >= 0 && R >= 1, "mt_bricks_step: E and R must be >= 1 and env0 >= 0");
-  MT_CHECK_ARG(T >= 1 && t >= 0 && t < T, "mt_bricks_step: t must be in [0, T)");
-  MT_CHECK_ARG(tab_rep && a_idx && r_idx && state && prev && out && reward_out && over_out && rm_out,
-               "mt_bricks_step: null argument");
-  MT_CHECK_ARG((frames_out == nullptr) == (push_count_out == nullptr),
-               "mt_bricks_step: frames_out and push_count_out go together");
-  MT_CHECK_ARG(prev != out, "mt_bricks_step: out may not alias prev");
-  MT_CHECK_ARG((((uintptr_t)prev | (uintptr_t)out | (uintptr_t)frames_out) & 15) == 0 && ((uintptr_t)state & 7) == 0,
-               "mt_bricks_step: misaligned buffer");
-  if (depth == 1)
-    hipLaunchKernelGGL((bricks_kernel<1, false>), dim3(E), dim3(256), 0, (hipStream_t)stream, *cfg, seed, env0, tab_rep,
-                       R, a_idx, r_idx, state, prev, out, frames_out, push_count_out, reward_out, over_out, rm_out, t, T);
-  else
-    hipLaunchKernelGGL((bricks_kernel<3, false>), dim3(E), dim3(256), 0, (hipStream_t)stream, *cfg, seed, env0, tab_rep,
-                       R, a_idx, r_idx, state, prev, out, frames_out, push_count_out, reward_out, over_out, rm_out, t, T);
-  MT_LAUNCHED();
-  return MT_OK;
+  return game_step<Bricks>(cfg, seed, env0, E, depth, tab_rep, R, a_idx, r_idx, state, prev, out, frames_out,
+                           push_count_out, reward_out, over_out, rm_out, t, T, stream);
 }
 
 extern "C" int mt_bricks_reset_host(const mt_bricks_config *cfg, uint64_t seed, uint64_t global_env, int depth,
                                     mt_bricks_state *state, uint8_t *out_state0) {
-  (void)seed;
-  (void)global_env;  // (a new game draws nothing: the first serve hashes them)
-  if (int rc = bricks_check(cfg, depth, "mt_bricks_reset_host")) return rc;
-  MT_CHECK_ARG(state != nullptr, "mt_bricks_reset_host: null state");
-  mt_bricks_state s = {};
-  BricksTrace tr = {};
-  bricks_new_game(*cfg, s, tr);
-  *state = s;
-  if (out_state0) {
-    if (depth == 1)
-      host_stack<1>(tr, nullptr, out_state0);
-    else
-      host_stack<3>(tr, nullptr, out_state0);
-  }
-  return MT_OK;
+  return game_reset_host<Bricks>(cfg, seed, global_env, depth, state, out_state0);
 }
 
 extern "C" int mt_bricks_step_host(const mt_bricks_config *cfg, uint64_t seed, uint64_t global_env, int depth,
                                    const int32_t *tab_rep, int R, int a, int r, mt_bricks_state *state,
                                    const uint8_t *prev, uint8_t *out, uint8_t *frames_out, int32_t *push_count_out,
                                    float *reward_out, float *over_out) {
-  if (int rc = bricks_check(cfg, depth, "mt_bricks_step_host")) return rc;
-  MT_CHECK_ARG(tab_rep && R >= 1 && state && reward_out && over_out, "mt_bricks_step_host: null argument or R < 1");
-  MT_CHECK_ARG(!out || (prev && prev != out), "mt_bricks_step_host: out needs a prev that it does not alias");
-  a = a < 0 ? 0 : (a > 3 ? 3 : a);
-  r = r < 0 ? 0 : (r > R - 1 ? R - 1 : r);
-  int rep = tab_rep[r];
-  rep = rep < 0 ? 0 : (rep > 255 ? 255 : rep);
-  mt_bricks_state s = *state;
-  s.bricks_hi &= kBricksFullHi;
-  s.reserved = 0;
-  BricksTrace tr = {};
-  int reward;
-  bool over;
-  bricks_macro_step(*cfg, seed, global_env, s, a, rep + 1, tr, &reward, &over);
-  *state = s;
-  *reward_out = (float)reward;
-  *over_out = over ? 1.f : 0.f;
-  if (push_count_out) *push_count_out = tr.count;
-  if (out) {
-    if (depth == 1)
-      host_stack<1>(tr, prev, out);
-    else
-      host_stack<3>(tr, prev, out);
-  }
-  if (frames_out) {
-    if (depth == 1)
-      host_frames<1>(tr, frames_out);
-    else
-      host_frames<3>(tr, frames_out);
-  }
-  return MT_OK;
+  return game_step_host<Bricks>(cfg, seed, global_env, depth, tab_rep, R, a, r, state, prev, out, frames_out,
+                                push_count_out, reward_out, over_out);
 }

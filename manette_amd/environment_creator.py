@@ -6,6 +6,7 @@ reads from the ROM; sizes below are ALE's minimal action sets, cross-checked whe
 reference's pretrained checkpoints pin a head width). If ale_python_interface becomes
 importable, an ALE-backed emulator can be plugged in behind the same create_environment().
 """
+from . import device_game
 from .synthetic import SyntheticBank, SyntheticEmulator
 
 MINIMAL_ACTIONS = {
@@ -21,9 +22,10 @@ MINIMAL_ACTIONS = {
 
 
 # games with a device-resident environment (--runner device): the game lives in HBM, one kernel per macro-step
-DEVICE_GAMES = ('catch', 'bricks')
+# (manette_amd/device_game.py: the same rule on the host, Game.Emulator, and in HBM, Game.Device)
+DEVICE_GAMES = tuple(n for n, g in device_game.games().items() if not g.reference)
 # and the reference's own game with one (its rule is tetris.py's, not this project's)
-REFERENCE_DEVICE_GAMES = ('tetris',)
+REFERENCE_DEVICE_GAMES = tuple(n for n, g in device_game.games().items() if g.reference)
 ALL_DEVICE_GAMES = DEVICE_GAMES + REFERENCE_DEVICE_GAMES
 
 
@@ -39,36 +41,13 @@ class EnvironmentCreator(object):
         self.game = game
         self.rgb = bool(getattr(args, 'rgb', False))
         self.rank_offset = int(getattr(args, 'env_id_offset', 0))
-        if game == 'catch':
-            # a real game (manette_amd/catch.py): the same rule on the host (CatchEmulator) and in HBM
-            # (create_device_env), both keyed on (--seed, global env id)
-            from . import catch
-            self.num_actions = catch.NUM_ACTIONS
-            self.catch_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
-                                   lives=int(getattr(args, 'catch_lives', catch.DEFAULT_LIVES)),
-                                   max_balls=int(getattr(args, 'catch_max_balls', catch.DEFAULT_MAX_BALLS)))
-            self.create_environment = lambda i: catch.CatchEmulator(self.rank_offset + i, **self.catch_args)
-            return
-        if game == 'bricks':
-            # the second real game (manette_amd/bricks.py), through the same two faces
-            from . import bricks
-            self.num_actions = bricks.NUM_ACTIONS
-            self.bricks_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
-                                    lives=int(getattr(args, 'bricks_lives', bricks.DEFAULT_LIVES)),
-                                    max_nexts=int(getattr(args, 'bricks_max_nexts', bricks.DEFAULT_MAX_NEXTS)),
-                                    serve_wait=int(getattr(args, 'bricks_serve_wait', bricks.DEFAULT_SERVE_WAIT)))
-            self.create_environment = lambda i: bricks.BricksEmulator(self.rank_offset + i, **self.bricks_args)
-            return
-        if game == 'tetris':
-            # the reference's own game (manette_amd/tetris.py), through the same two faces
-            from . import tetris
-            self.num_actions = tetris.NUM_ACTIONS
-            wait = tetris.RANDOM_START_WAIT if getattr(args, 'random_start', False) else tetris.DEFAULT_MAX_START_WAIT
-            self.tetris_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
-                                    max_nexts=int(getattr(args, 'tetris_max_nexts', tetris.DEFAULT_MAX_NEXTS)),
-                                    speed=int(getattr(args, 'tetris_speed', tetris.DEFAULT_SPEED)),
-                                    max_start_wait=wait)
-            self.create_environment = lambda i: tetris.TetrisEmulator(self.rank_offset + i, **self.tetris_args)
+        self.device_game = device_game.games().get(game)
+        if self.device_game is not None:
+            # a real game: both faces are keyed on (--seed, global env id)
+            self.num_actions = self.device_game.num_actions
+            self.game_args = dict(seed=int(getattr(args, 'seed', 0)), rgb=self.rgb,
+                                  **self.device_game.config_from_args(args))
+            self.create_environment = lambda i: self.device_game.Emulator(self.rank_offset + i, **self.game_args)
             return
         self.num_actions = MINIMAL_ACTIONS.get(game, 18)
         self.create_environment = lambda i: SyntheticEmulator(self.rank_offset + i, self.num_actions,
@@ -76,17 +55,10 @@ class EnvironmentCreator(object):
 
     def create_device_env(self, n_envs, tab_rep, device='cuda'):
         """Envs [0, n_envs) of this rank (global ids offset by rank) as a device-resident environment."""
-        if not has_device_env(self.game):
+        if self.device_game is None:
             raise ValueError('game %r has no device environment (--runner device serves: %s)'
                              % (self.game, ', '.join(ALL_DEVICE_GAMES)))
-        if self.game == 'bricks':
-            from . import bricks
-            return bricks.BricksDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.bricks_args)
-        if self.game == 'tetris':
-            from . import tetris
-            return tetris.TetrisDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.tetris_args)
-        from . import catch
-        return catch.CatchDevice(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.catch_args)
+        return self.device_game.Device(n_envs, tab_rep, env0=self.rank_offset, device=device, **self.game_args)
 
     def create_bank(self, first_local, n_envs):
         """Native bank of envs [first_local, first_local+n) (global ids offset by rank)."""

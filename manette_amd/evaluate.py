@@ -1,7 +1,7 @@
 """Device-resident evaluation of a policy on a device game (include/manette_hip.h, "Device evaluation").
 
-DeviceEvaluator plays K episodes on each of N envs of Catch or Bricks with a fixed chooser and a draw
-stream of its own, every run on the same games (a run resets the envs, so their ball / serve streams
+DeviceEvaluator plays K episodes on each of N envs of a device game with a fixed chooser and a draw
+stream of its own, every run on the same games (a run resets the envs, so their draw streams
 start from counter 0 again). A macro-step is forward (infer) -> draw -> env kernel -> mt_eval_step, all
 enqueued; the host looks at the device's word block once per `check_every` steps. The per-episode
 results stay in device tables until the run ends; mt_eval_summarize reduces them in a fixed order.
@@ -12,7 +12,6 @@ does) from the 'eval' workspace's own dropout state; LSTM runs on an [N][5][fram
 mt_memory_push after each env step (a window is zeroed at an episode end, as in training).
 """
 import ctypes as C
-import importlib
 
 import numpy as np
 import torch
@@ -96,8 +95,7 @@ class DeviceEvaluator(object):
         self.draw_seed = int(draw_seed) & 0xffffffffffffffff
         self.graph = bool(graph)
         self.check_every = max(2, int(check_every) + (int(check_every) & 1))  # even: the ping-pong parity closes
-        bound = importlib.import_module(type(self.env).__module__).max_episode_nexts(self.env.cfg)
-        self.max_macro_steps = K * bound + 1 if max_macro_steps is None else int(max_macro_steps)
+        self.max_macro_steps = K * self.env.max_episode_nexts() + 1 if max_macro_steps is None else int(max_macro_steps)
         self.record = bool(record)
         self.lstm = network.arch == 'LSTM'
         self.bayes = network.arch == 'BAYESIAN'

@@ -59,7 +59,7 @@ def check_arch_flags(args):
     --bayes_native switches the BAYESIAN arch to the native macro-step and the captured, fused update."""
     if getattr(args, 'bayes_native', False) and getattr(args, 'arch', None) != 'BAYESIAN':
         raise ValueError('--bayes_native is for --arch BAYESIAN (got --arch %s)' % getattr(args, 'arch', None))
-    # --runner device: the game lives in HBM (manette_amd/catch.py); games without a device env and the
+    # --runner device: the game lives in HBM (manette_amd/device_game.py); games without a device env and the
     # LSTM frame store are refused; a device game has no native (host-thread) bank
     from .environment_creator import ALL_DEVICE_GAMES, has_device_env
     runner, game = getattr(args, 'runner', 'native'), getattr(args, 'game', 'pong')

@@ -28,74 +28,49 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def random_policy_mean(episodes, lives, max_balls, seed=0):
-    """Mean return of uniform-random actions over `episodes` episodes of env 0 (mt_catch_step_host)."""
-    from manette_amd import _lib, catch
-    cfg = catch.config(lives, max_balls)
-    st = _lib.mt_catch_state()
-    catch.host_reset(cfg, seed, 0, 1, st)
-    rs = np.random.RandomState(12345)
+def policy_mean(game, choose, episodes, seed, per_next=False, **cfg):
+    """Mean return (per_next: mean of return / length) over `episodes` episodes of env 0 of `game` on its host
+    face (mt_<game>_step_host, no rendering) under choose() -> action."""
+    from manette_amd import device_game
+    g = device_game.games()[game]
+    c = g.config(**cfg)
+    st = g.state_class()
+    g.host_reset(c, seed, 0, 1, st)
     tab = np.zeros(1, np.int32)
-    rets, ret = [], 0.0
-    while len(rets) < episodes:
-        rw, over, _ = catch.host_step(cfg, seed, 0, 1, tab, int(rs.randint(3)), 0, st)
-        ret += rw
-        if over:
-            rets.append(ret)
-            ret = 0.0
-    return float(np.mean(rets))
-
-
-def bar(lives, max_balls, episodes=100, seed=0):
-    return 0.5 * (random_policy_mean(episodes, lives, max_balls, seed) + max_balls)
-
-
-def bricks_random_policy_mean(episodes=100, seed=0, **cfg):
-    """Mean return of uniform-random actions over `episodes` episodes of env 0 (mt_bricks_step_host)."""
-    from manette_amd import _lib, bricks
-    c = bricks.config(**cfg)
-    st = _lib.mt_bricks_state()
-    bricks.host_reset(c, seed, 0, 1, st)
-    rs = np.random.RandomState(12345)
-    tab = np.zeros(1, np.int32)
-    rets, ret = [], 0.0
-    while len(rets) < episodes:
-        rw, over, _ = bricks.host_step(c, seed, 0, 1, tab, int(rs.randint(4)), 0, st)
-        ret += rw
-        if over:
-            rets.append(ret)
-            ret = 0.0
-    return float(np.mean(rets))
-
-
-def bricks_bar(episodes=100, seed=0, **cfg):
-    return 4.0 * bricks_random_policy_mean(episodes, seed, **cfg)
-
-
-def tetris_policy_rate(choose, episodes=100, seed=0, **cfg):
-    """Mean of return / length over `episodes` episodes of env 0 (mt_tetris_step_host) under choose() -> action."""
-    from manette_amd import _lib, tetris
-    c = tetris.config(**cfg)
-    st = _lib.mt_tetris_state()
-    tetris.host_reset(c, seed, 0, 1, st)
-    tab = np.zeros(1, np.int32)
-    rates, ret, n = [], 0.0, 0
-    while len(rates) < episodes:
-        rw, over, _ = tetris.host_step(c, seed, 0, 1, tab, choose(), 0, st)
+    means, ret, n = [], 0.0, 0
+    while len(means) < episodes:
+        rw, over, _ = g.host_step(c, seed, 0, 1, tab, choose(), 0, st)
         ret += rw
         n += 1
         if over:
-            rates.append(ret / n)
+            means.append(ret / n if per_next else ret)
             ret, n = 0.0, 0
-    return float(np.mean(rates))
+    return float(np.mean(means))
+
+
+def _uniform(num_actions):
+    rs = np.random.RandomState(12345)
+    return lambda: int(rs.randint(num_actions))
+
+
+def bar(lives, max_balls, episodes=100, seed=0):
+    """Halfway between the uniform-random policy's mean return and max_balls."""
+    return 0.5 * (policy_mean('catch', _uniform(3), episodes, seed, lives=lives, max_balls=max_balls) + max_balls)
+
+
+def bricks_bar(episodes=100, seed=0, **cfg):
+    """4 x the uniform-random policy's mean return."""
+    return 4.0 * policy_mean('bricks', _uniform(4), episodes, seed, **cfg)
+
+
+def tetris_policy_rate(choose, episodes=100, seed=0, **cfg):
+    return policy_mean('tetris', choose, episodes, seed, per_next=True, **cfg)
 
 
 def tetris_bar(episodes=100, seed=0, **cfg):
     """The midpoint between the uniform-random policy's reward per next and the always-drop policy's."""
-    rs = np.random.RandomState(12345)
-    rand = tetris_policy_rate(lambda: int(rs.randint(5)), episodes, seed, **cfg)
-    drop = tetris_policy_rate(lambda: 3, episodes, seed, **cfg)
-    return 0.5 * (rand + drop)
+    return 0.5 * (tetris_policy_rate(_uniform(5), episodes, seed, **cfg) +
+                  tetris_policy_rate(lambda: 3, episodes, seed, **cfg))
 
 
 def make_learner(folder, seed, ec=32, arch='NIPS', lives=3, max_balls=20, sampling='device', max_rep=0, nb=1,

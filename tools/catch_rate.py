@@ -1,4 +1,4 @@
-"""Throughput of the device-resident Catch (manette_amd/catch.py).
+"""Throughput of the device-resident games (manette_amd/device_game.py), Catch by default.
 
   kernel   mt_catch_step alone at E = 32 / 64, gray / RGB, R = 1 / 11, as a hipGraph of back-to-back
            calls between device events (bench.graph_time), beside mt_preprocess_resized on the same
@@ -37,78 +37,58 @@ def _tag(game):
     return {} if game == 'catch' else {'game': game}  # (the default's lines are what they were)
 
 
+# what a --game run times, in this order, and the macro-steps each game plays first (catch: the yardstick's
+# pushes; bricks: balls in play, the first nexts serve; tetris: some way into its episodes)
+MEASURED = {'catch': ('catch',), 'bricks': ('catch', 'bricks'), 'tetris': ('catch', 'bricks', 'tetris')}
+WARM_STEPS = {'catch': 1, 'bricks': 8, 'tetris': 40}
+
+
 def kernel_times(inner=50, reps=5, game='catch'):
     import torch
     import bench
-    from manette_amd import bricks, catch, network as devnet, tetris
+    from manette_amd import device_game, network as devnet
+    games = device_game.games()
     for E in (32, 64):
         for depth in (1, 3):
             for R in (1, 11):
                 tab = [0] if R == 1 else [i for i in range(11)]
-                dev = catch.CatchDevice(E, tab, seed=1, rgb=depth == 3)
                 z = lambda *s, **k: torch.zeros(*s, device='cuda', **k)
                 bufs = [z(E, 84, 84, 4 * depth, dtype=torch.uint8), z(E, 84, 84, 4 * depth, dtype=torch.uint8)]
                 rs = np.random.RandomState(0)
-                a = torch.from_numpy(rs.randint(0, 3, E).astype(np.int32)).cuda()
-                r = torch.from_numpy(rs.randint(0, R, E).astype(np.int32)).cuda()
                 reward, over, rm = z(E), z(E), z(2, 1, E)
                 frames, count = z(4 * E, 84, 84, depth, dtype=torch.uint8), z(E, dtype=torch.int32)
                 off = torch.arange(0, 4 * E, 4, dtype=torch.int32, device='cuda')
-                dev.reset(bufs[0])
-                dev.step(a, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)  # the yardstick's pushes
                 k = [0]
-
-                def step():
-                    dev.step(a, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
-                    k[0] += 1
 
                 def stack():
                     devnet.preprocess(frames, off, count, E, depth, None, None, bufs[k[0] & 1], bufs[1 - (k[0] & 1)],
                                       resized=True)
                     k[0] += 1
 
-                t_env = bench.graph_time(step, inner, reps)
-                t_stack = bench.graph_time(stack, inner, reps)
-                if game in ('bricks', 'tetris'):  # the same buffers, indices and table under the other game (a in 0..3)
-                    bdev = bricks.BricksDevice(E, tab, seed=1, rgb=depth == 3)
-                    ab = torch.from_numpy(rs.randint(0, 4, E).astype(np.int32)).cuda()
-                    bdev.reset(bufs[0])
-                    for _ in range(8):  # (balls in play: the first nexts serve)
-                        bdev.step(ab, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)
+                us, r = {}, None
+                for name in MEASURED[game]:  # the same buffers, repetition indices and table under every game
+                    dev = games[name].Device(E, tab, seed=1, rgb=depth == 3)
+                    a = torch.from_numpy(rs.randint(0, games[name].num_actions, E).astype(np.int32)).cuda()
+                    if r is None:
+                        r = torch.from_numpy(rs.randint(0, R, E).astype(np.int32)).cuda()
+                    dev.reset(bufs[0])
+                    for _ in range(WARM_STEPS[name]):
+                        dev.step(a, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)
 
-                    def bstep():
-                        bdev.step(ab, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
+                    def step():
+                        dev.step(a, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
                         k[0] += 1
 
-                    t_b = bench.graph_time(bstep, inner, reps)
-                    extra = {}
-                    if game == 'tetris':  # and under the third game (a in 0..4), some way into its episodes
-                        tdev = tetris.TetrisDevice(E, tab, seed=1, rgb=depth == 3)
-                        at = torch.from_numpy(rs.randint(0, 5, E).astype(np.int32)).cuda()
-                        tdev.reset(bufs[0])
-                        for _ in range(40):
-                            tdev.step(at, r, bufs[0], bufs[1], reward, over, rm, 0, 1, frames, count)
-
-                        def tstep():
-                            tdev.step(at, r, bufs[k[0] & 1], bufs[1 - (k[0] & 1)], reward, over, rm, 0, 1)
-                            k[0] += 1
-
-                        t_t = bench.graph_time(tstep, inner, reps)
-                        extra = dict(tetris_step_us=round(float(np.median(t_t)), 2),
-                                     tetris_step_all=[round(x, 2) for x in t_t])
-                    print(json.dumps(dict(what='kernel', game=game, E=E, depth=depth, R=R, **extra,
-                                          bricks_step_us=round(float(np.median(t_b)), 2),
-                                          catch_step_us=round(float(np.median(t_env)), 2),
-                                          preprocess_resized_us=round(float(np.median(t_stack)), 2),
-                                          bricks_step_all=[round(x, 2) for x in t_b],
-                                          catch_step_all=[round(x, 2) for x in t_env],
-                                          preprocess_resized_all=[round(x, 2) for x in t_stack])), flush=True)
-                    continue
-                print(json.dumps(dict(what='kernel', E=E, depth=depth, R=R, mean_pushes=float(count.float().mean()),
-                                      catch_step_us=round(float(np.median(t_env)), 2),
-                                      preprocess_resized_us=round(float(np.median(t_stack)), 2),
-                                      catch_step_all=[round(x, 2) for x in t_env],
-                                      preprocess_resized_all=[round(x, 2) for x in t_stack])), flush=True)
+                    us[name + '_step'] = bench.graph_time(step, inner, reps)
+                    if name == 'catch':  # beside mt_preprocess_resized on catch's frames and push counts
+                        mean_pushes = float(count.float().mean())
+                        us['preprocess_resized'] = bench.graph_time(stack, inner, reps)
+                line = dict(what='kernel', **_tag(game), E=E, depth=depth, R=R)
+                if game == 'catch':
+                    line['mean_pushes'] = mean_pushes
+                line.update({key + '_us': round(float(np.median(t)), 2) for key, t in us.items()})
+                line.update({key + '_all': [round(x, 2) for x in t] for key, t in us.items()})
+                print(json.dumps(line), flush=True)
 
 
 def rollout_rates(updates=300, rounds=3, ec=32, game='catch'):
